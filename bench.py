@@ -7,14 +7,19 @@ one whole tspws_main-equivalent call on HBM-resident traces: partial stacks -> (
 CWTs + phase stack -> weight -> 2 inverse CWTs -> float outputs.  Weak scaling: every rank holds its own shard of an
 (N x traces)-trace ensemble.  `--config cfg5` is BASELINE configs[4]: 12 500 traces per GPU (100 000 at N=8).
 
-    python bench.py                         one GPU: headline line + roofline + CPU baseline + the other configs
+    python bench.py                         one GPU: headline line + roofline of the timed steps
+    python bench.py --full                  ... + CPU baseline + D2H-inclusive figure + host path + the other configs
     python bench.py --gpus 8                starts its own 8 ranks (torch.distributed.run, one per GPU, RCCL) -- no GPU call
                                             is made in the parent; under an external torchrun (WORLD_SIZE set) it just runs
     python bench.py --gpus 8 --config cfg5  BASELINE configs[4]
+    python bench.py --dump-outputs DIR      also writes the last timed step's outputs: DIR/ls.npy, DIR/tsPWS.npy (float32 [N])
 
-Prints ONE JSON line (the driver contract).  N=1 adds: `cpu_baseline` (the reference OpenMP path on this host),
-`end_to_end_host_path` (the drop-in tspws_main on host buffers, PCIe included) and `other_configs` (cfg2 single-stage,
-cfg4 Mexican hat + jackknife, each with its roofline fraction and its error against the reference on a bounded sub-batch).
+Prints ONE JSON line (the driver contract).  A plain run sets up, warms up, times --steps steps and prints the headline
+(`value`, `ms_per_step`, the roofline of the streaming stage of those same steps).  `--full` adds, after the headline timing:
+N=1: `with_output_d2h` (the same loop with the D2H copies of the outputs), `cpu_baseline` (the reference OpenMP path on this
+host), `end_to_end_host_path` (the drop-in tspws_main on host buffers, PCIe included) and `other_configs` (cfg2 single-stage,
+cfg4 Mexican hat + jackknife, each with its roofline fraction and its error against the reference on a bounded sub-batch);
+N>1: `cpu_baseline` on rank 0's shard, the other two reduction schedules (`schedules`) and the strong-scaling leg.
 """
 import argparse
 import ctypes as C
@@ -47,22 +52,30 @@ def parse():
     ap.add_argument("--schedule", choices=["single", "split", "sharded-finish"], default=None,
                     help="N > 1: placement of the one logical reduction of P[K][N] (ts-pws_amd.stack_sharded): single = ONE all-reduce + redundant "
                          "finish (north_star's wording; default), split = two halves overlapped with streaming / transforms, sharded-finish = "
-                         "pieces K-2 | 2 + scale-sharded finish; the other two are timed in the same run as well (`schedules`)")
+                         "pieces K-2 | 2 + scale-sharded finish; with --full the other two are timed in the same run as well (`schedules`)")
     ap.add_argument("--shard-of", type=int, default=None,
                     help="one GPU only: treat the traces as rank 0's shard of an ensemble this many times larger (cfg5 on one GPU: 12 500 of 100 000; "
                          "default 8 for --config cfg5 --gpus 1, else 1)")
     ap.add_argument("--strong-total", type=int, default=None,
-                    help="N > 1: after the weak-scaling legs, one more leg with this many traces IN ALL, sharded over the ranks (strong scaling; default "
+                    help="N > 1, --full: after the weak-scaling legs, one more leg with this many traces IN ALL, sharded over the ranks (strong scaling; default "
                          "100 000 = BASELINE configs[4] when the per-GPU size is the default one, else off; 0: off)")
     ap.add_argument("--collective-timeout", type=int, default=180, help="N > 1: seconds after which a hung collective fails the run")
     ap.add_argument("--leg-deadline", type=int, default=60,
-                    help="N > 1: seconds an A/B leg (another schedule, the strong-scaling leg) may take before rank 0 prints the line it has and every rank exits")
+                    help="N > 1, --full: seconds an A/B leg (another schedule, the strong-scaling leg) may take before rank 0 prints the line it has and every rank exits")
     ap.add_argument("--inject-hang", choices=["single", "split", "sharded-finish", "strong"], default=None,
                     help="TEST ONLY (tests/test_cli_gpu.py): the last rank never enters this optional leg -- its peers sit in the leg's first collective until "
                          "the deadline prints the line measured so far")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline, host-path and other-config legs")
-    ap.add_argument("--no-extra", action="store_true", help="skip the host-path and other-config legs only")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline timing, also run the legs beyond it: CPU baseline, D2H-inclusive loop, host path and other configs "
+                         "(N = 1); CPU baseline on rank 0's shard, the other schedules and the strong-scaling leg (N > 1)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline, host-path and other-config legs")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the host-path and other-config legs only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (ls, tsPWS: float32 [samples]) as DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def self_launch(args):
@@ -278,7 +291,9 @@ def run(args):
 
     step, ev, launches, schedule = make_leg(schedule, X, first, mtr_global)
     dt = time_leg(step, args.warmup)
-    out_sha = digest() if world > 1 else None
+    out_sha = digest() if (world > 1 and args.full) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ls=ls, tsPWS=ts)
 
     if single:
         stage_ms, call_ms = plan.profile_read()
@@ -343,12 +358,12 @@ def run(args):
 
     if not single:
         res["per_rank_ms"] = {"columns": ["stream", "exposed_collective", "finish"], "ranks": rank_columns(ev), "schedule": schedule if world > 1 else None}
-    if world > 1 and rank == 0 and not args.no_cpu:
+    if world > 1 and rank == 0 and args.full and not args.no_cpu:
         # N > 1: the reference OpenMP path on THIS node's host cores beside the N-GPU number, in the same run (north_star): rank 0
         # runs it on its own shard after the timed loop (the other ranks wait in the barrier below), and checks its shard-local
         # partial stacks -- global group index, before any reduction -- against direct FP64 sums of the same traces
         res["cpu_baseline"] = cpu_baseline_shard(abi, plan, X, abi.default_params(Kmax=K, unbiased=1), N, K, mtr_local, first, mtr_global, red)
-    if world > 1:
+    if world > 1 and args.full:
         # The driver's ONE multi-GPU run as an A/B: every schedule in the same invocation -- same plan, same traces, args.steps timed
         # steps each between barriers.  `value` / `ms_per_step` above stay the default schedule's; `single` (north_star's wording) and
         # `split` end in the one-GPU call's accumulation order, so their outputs are bit-identical to it (output_sha1: ls || tsPWS on rank 0).
@@ -413,7 +428,7 @@ def run(args):
                                      "traces_total": total, "traces_on_rank0": cnt if rank == 0 else None, "schedule": eff5, "ms_per_step": d5 / args.steps * 1e3,
                                      "value": total * N * args.steps / d5, "unit": "samples/s", "scaling": "strong", "per_rank_ms": cols5}
             del X5
-    if world == 1 and shard_of == 1 and rank == 0:
+    if world == 1 and shard_of == 1 and rank == 0 and args.full:
         res["with_output_d2h"] = with_d2h(torch, plan, X, ls, ts, N, mtr_local, args.steps)
         if not args.no_cpu:
             Xh = X.cpu().numpy()
@@ -428,6 +443,14 @@ def run(args):
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(path, **outputs):
+    """The arrays a caller of the timed path receives, as float32 .npy files (torch tensors on the device)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float32))
 
 
 def file_sha256(path):

@@ -5,7 +5,8 @@
 TAG=${1:-rXX}
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 mkdir -p $R/gpurun_out
-python3 $R/bench.py > $R/gpurun_out/${TAG}_bench_line.json 2> $R/gpurun_out/${TAG}_bench.err
+OUT=$_   # the output directory just made
+python3 $R/bench.py --full > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench.err   # --full: the line with the CPU baseline and the other configs
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_$TAG -o b -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu > $R/gpurun_out/${TAG}_bench_prof.log 2>&1
 cd $R

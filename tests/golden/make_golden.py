@@ -8,6 +8,7 @@ these arrays -- inputs from this repo's own seeded generator, outputs from the
 reference library -- are what pins the oracle and the HIP path.
 
     python tests/golden/make_golden.py          # rewrites tests/golden/*.npz
+    python tests/golden/make_golden.py extra    # extra.npz only (synth50: ref_synth50.npz only)
 
 Fixtures are data only: inputs and expected outputs.
 """
@@ -270,8 +271,21 @@ def extra():
     print("extra fixtures written")
 
 
+def synth50():
+    """The reference's whole-call outputs on 50 x 8192 seeded traces (the inputs are abi.synth_traces(50, 8192, seed=8), regenerated by
+    the test): what tests/test_hip_parity.py::test_tspws_main_vs_reference_outputs holds tspws_main to."""
+    lib = ref_lib()
+    P = abi.default_params
+    X = abi.synth_traces(50, 8192, seed=8)
+    ex = {}
+    for name, p in (("morlet", P()), ("morlet_k10_unbiased", P(Kmax=10, unbiased=1)), ("mexhat", P(type=-3))):
+        ex.update(main_case(lib, name, p, X))
+    np.savez_compressed(os.path.join(HERE, "ref_synth50.npz"), **ex)
+    print("synth50 fixtures written")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "extra":
-        extra()
+    if len(sys.argv) > 1 and sys.argv[1] in ("extra", "synth50"):
+        {"extra": extra, "synth50": synth50}[sys.argv[1]]()
     else:
         main()

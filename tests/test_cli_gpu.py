@@ -153,7 +153,7 @@ def _bench(args, env_extra=None, timeout=600):
 def test_bench_starts_its_own_ranks():
     """`bench.py --gpus 2` without a launcher around it: the parent starts two ranks before touching the GPU (here both on the
     one GPU of the box, collectives over gloo), rank 0's JSON line comes back through the parent."""
-    r = _bench(["--gpus", "2", "--traces", "64", "--samples", "4096", "--steps", "3", "--warmup", "1", "--strong-total", "300"], {"BENCH_BACKEND": "gloo"})
+    r = _bench(["--gpus", "2", "--traces", "64", "--samples", "4096", "--steps", "3", "--warmup", "1", "--strong-total", "300", "--full"], {"BENCH_BACKEND": "gloo"})
     assert r["n_gpus"] == 2 and r["config"]["world_size"] == 2 and r["config"]["backend"] == "gloo"
     # the one multi-GPU run is an A/B of the three placements of the reduction (same plan, same traces, `steps` timed steps each); the
     # headline fields are the default schedule's; `single` -- north_star's ONE all-reduce -- ends bit-identical to the one-GPU call
@@ -194,7 +194,7 @@ def test_bench_prints_its_line_when_an_optional_leg_hangs(leg):
     optional leg runs under a deadline; when the last rank never shows up in a leg's collective, rank 0 prints the line measured so far --
     headline, roofline, per-rank columns, CPU baseline, the legs that did finish -- names the leg, and every rank leaves with status 0."""
     r = _bench(["--gpus", "2", "--traces", "64", "--samples", "4096", "--steps", "2", "--warmup", "1", "--strong-total", "200", "--leg-deadline", "6",
-                "--inject-hang", leg], {"BENCH_BACKEND": "gloo"})
+                "--inject-hang", leg, "--full"], {"BENCH_BACKEND": "gloo"})
     assert r["aborted_leg"]["leg"] == ("schedule split" if leg == "split" else "strong scaling") and r["aborted_leg"]["deadline_s"] == 6
     assert r["value"] > 0 and r["n_gpus"] == 2 and "cpu_baseline" in r and "roofline" in r and len(r["per_rank_ms"]["ranks"]) == 2
     assert r["schedules"]["single"]["is_default"] and r["schedules"]["single"]["ms_per_step"] > 0
@@ -208,7 +208,7 @@ def test_bench_prints_its_line_when_an_optional_leg_hangs(leg):
 def test_bench_single_gpu_line_has_the_contract_keys():
     """One GPU, small size: the line carries the contract keys, the roofline object, the per-step statistics, the D2H-inclusive
     figure and the CPU baseline with the full-size comparison against it."""
-    r = _bench(["--traces", "200", "--samples", "8192", "--steps", "5", "--warmup", "2", "--no-extra"])
+    r = _bench(["--traces", "200", "--samples", "8192", "--steps", "5", "--warmup", "2", "--no-extra", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
               "config", "roofline", "cpu_baseline", "step_ms_gpu", "with_output_d2h"):
         assert k in r, k
@@ -216,6 +216,28 @@ def test_bench_single_gpu_line_has_the_contract_keys():
     assert set(("bound", "achieved", "peak", "unit", "frac", "traffic")) <= set(r["roofline"])
     assert r["cpu_baseline"]["rc"] == 0 and r["cpu_baseline"]["gpu_vs_cpu_relerr"]["tsPWS"] < 1e-5 and r["cpu_baseline"]["gpu_vs_cpu_relerr"]["ls"] < 1e-5
     assert r["step_ms_gpu"]["n"] == 5
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """Without --full the line holds the headline of the timed steps only (no leg beyond them); --dump-outputs writes what the last
+    timed step computed: the outputs of the same call on the same seeded traces."""
+    import torch
+    out = tmp_path / "out"
+    r = _bench(["--traces", "200", "--samples", "8192", "--steps", "4", "--warmup", "1", "--dump-outputs", str(out)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "step_ms_gpu"):
+        assert k in r, k
+    for k in ("cpu_baseline", "with_output_d2h", "end_to_end_host_path", "other_configs"):
+        assert k not in r, k
+    assert r["steps"] == 4 and r["step_ms_gpu"]["n"] == 4
+    assert r["value"] * r["ms_per_step"] * 1e-3 == pytest.approx(200 * 8192, rel=1e-9)
+    ls, ts = np.load(out / "ls.npy"), np.load(out / "tsPWS.npy")
+    assert ls.dtype == np.float32 and ts.dtype == np.float32 and ls.shape == ts.shape == (8192,)
+    pl = tspws.Plan(tspws.resolve(abi.default_params(Kmax=10, unbiased=1), 8192), 8192)
+    want = pl.stack_single(tspws.synth(200, 8192, seed=1))
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(ls, want[0].cpu().numpy())
+    np.testing.assert_array_equal(ts, want[1].cpu().numpy())
 
 
 @pytest.mark.parametrize("bad,field", [(2, "dt"), (5, "dt"), (3, "beg")])

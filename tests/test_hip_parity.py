@@ -269,16 +269,13 @@ def test_tspws_main_vs_oracle(lib, kw, mtr, N):
     assert abi.relerr(a["tsPWS"], b["tsPWS"]) < TOL32
 
 
-def test_tspws_main_vs_reference_if_built(lib):
-    ref = abi.ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built on this machine")
+def test_tspws_main_vs_reference_outputs(lib):
+    """50 x 8192 seeded traces against the reference's own outputs (tests/golden/ref_synth50.npz, from make_golden.py synth50)."""
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_synth50.npz"))
     X = abi.synth_traces(50, 8192, seed=8)
-    for kw in (dict(), dict(Kmax=10, unbiased=1), dict(type=-3)):
-        p = abi.default_params(**kw)
-        a = abi.run_main(lib.tspws_main, p, X)
-        b = abi.run_main(ref.tspws_main, p, X)
-        assert abi.relerr(a["ls"], b["ls"]) < TOL32 and abi.relerr(a["tsPWS"], b["tsPWS"]) < TOL32
+    for name, kw in (("morlet", dict()), ("morlet_k10_unbiased", dict(Kmax=10, unbiased=1)), ("mexhat", dict(type=-3))):
+        a = abi.run_main(lib.tspws_main, abi.default_params(**kw), X)
+        assert abi.relerr(a["ls"], g[f"{name}/ls"]) < TOL32 and abi.relerr(a["tsPWS"], g[f"{name}/tsPWS"]) < TOL32
 
 
 def test_jackknife_vs_oracle_many_traces(lib):
