@@ -229,6 +229,19 @@ int  tspws_hip_jackknife_finish(tspws_hip_plan *plan, const t_tsPWS *p, size_t m
                                 unsigned c_begin, unsigned c_end, float *d_ls_out, float *d_ts_out, unsigned *h_mtr_out,
                                 void *stream);
 
+/* ---- single-stage jackknife (an extension: the reference's tspws_jackknife_float, :711-716, is an empty stub) ---------------
+ * Host: classes of a selection sel[C][mtr] (1 = kept): the traces whose selection columns are identical, numbered in order of first
+ * appearance.  class_of_trace receives mtr class numbers, *ncls the class count; kept (may be NULL; room for C * mtr bytes at most)
+ * receives [C][*ncls] bytes, 1 = replica c keeps class k.  A jackknife selection has n or n + 1 classes (day-of-year bins). */
+int  tspws_selection_classes(const char *sel, unsigned C, size_t mtr, unsigned *class_of_trace, char *kept, unsigned *ncls);
+/* Device: the C replicas of a SINGLE-stage parameter set (two-stage: TSPWS_E_ARG).  Replica c is the single-stage resampling body
+ * (tspws_subsmpl_float, :501-610) on mask row c with K = M = K_c (its selected traces): tsPWS_out[c] = (float) Re_rec(weight(ST_c, PS_c));
+ * ls_out[c] = (float)((sum of the selected traces, FP64) * (1 / K_c)); h_mtr_out[c] = K_c; K_c = 0 gives zero rows.  Every trace is
+ * transformed once into per-class stacks, the replicas are sums of classes.  Same arguments as tspws_hip_jackknife; returns with its
+ * outputs complete. */
+int  tspws_hip_jackknife_single(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, size_t mtr,
+                                const char *h_sel, unsigned C, float *d_ls_out, float *d_ts_out, unsigned *h_mtr_out, void *stream);
+
 /* ---- random subsampling ---------------------------------------------------------------------- */
 /* Host: keep K of J traces at random with libc rand(), flipping whichever symbol is rarer.
  * SubsamplingPlan, ts_pws1f_lib.c:355-383 (same rand() call order, so the same masks from the same state). */

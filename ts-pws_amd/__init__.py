@@ -122,6 +122,8 @@ SYMBOLS = {
     "tspws_hip_jackknife_buffer": (_i, [_vp, _vp, _u, C.POINTER(_vp), C.POINTER(_sz)]),
     "tspws_hip_jackknife_local": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _u, _vp]),
     "tspws_hip_jackknife_finish": (_i, [_vp, _vp, _sz, _vp, _u, _u, _u, _vp, _vp, _vp, _vp]),
+    "tspws_selection_classes": (_i, [_vp, _u, _sz, _vp, _vp, C.POINTER(_u)]),
+    "tspws_hip_jackknife_single": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _u, _vp, _vp, _vp, _vp]),
     "tspws_subsampling_plan": (_i, [_vp, _sz, _sz]),
     "tspws_hip_subsample": (_i, [_vp, _vp, _vp, _sz, _sz, _u, _vp, _vp, _vp]),
     "tspws_hip_subsample_sel": (_i, [_vp, _vp, _vp, _sz, _sz, _u, _vp, _vp, _vp, _vp]),
@@ -371,6 +373,29 @@ class Plan:
               "stack_jackknife")
         return ls, ts, ls_out, ts_out, mtr_out
 
+    def jackknife_single(self, traces, sel, ls_out=None, ts_out=None, mtr_out=None):
+        """Single-stage jackknife replicas (tspws_hip_jackknife_single; the reference leaves these rows untouched).
+        `sel` = [C][mtr] int8 selection (jackknife_selection).  Returns ls_out[C][N], ts_out[C][N] (float32 cuda), mtr_out[C] (uint32)."""
+        import numpy as np
+        import torch
+        mtr, ld = self._traces(traces)
+        if not isinstance(sel, np.ndarray) or sel.ndim != 2 or sel.dtype not in (np.int8, np.uint8, np.bool_):
+            raise TspwsError("selection must be a 2-D int8 / uint8 / bool numpy array [C][mtr]")
+        sel = self._sel(sel, sel.shape[0], mtr)
+        Cn = sel.shape[0]
+        ls_out = torch.empty((Cn, self.N), dtype=torch.float32, device=traces.device) if ls_out is None else ls_out
+        ts_out = torch.empty((Cn, self.N), dtype=torch.float32, device=traces.device) if ts_out is None else ts_out
+        mtr_out = np.zeros(Cn, np.uint32) if mtr_out is None else mtr_out
+        if not isinstance(mtr_out, np.ndarray) or mtr_out.dtype != np.uint32 or mtr_out.shape != (Cn,) or not mtr_out.flags.c_contiguous:
+            raise TspwsError(f"mtr_out must be a contiguous uint32 numpy array of {Cn} entries")
+        for t, name in ((ls_out, "ls_out"), (ts_out, "ts_out")):
+            if t.dtype != torch.float32 or tuple(t.shape) != (Cn, self.N) or not t.is_contiguous() or not t.is_cuda or \
+                    (t.device.index or 0) != self.device:
+                raise TspwsError(f"{name} must be a contiguous float32 [{Cn}][{self.N}] tensor on cuda:{self.device}")
+        check(self.lib.tspws_hip_jackknife_single(self.h, C.byref(self.params), traces.data_ptr(), ld, mtr, sel.ctypes.data, Cn, ls_out.data_ptr(),
+                                                  ts_out.data_ptr(), mtr_out.ctypes.data, self._stream()), "jackknife_single")
+        return ls_out, ts_out, mtr_out
+
     def profile_begin(self, max_calls):
         """Record HIP events inside the next `max_calls` stack_single calls (start, end of the streaming stage, end)."""
         check(self.lib.tspws_hip_profile_begin(self.h, max_calls), "profile_begin")
@@ -600,6 +625,39 @@ def _as_tensor(ptr, count, dtype, device):
         __cuda_array_interface__ = {"shape": (count,), "typestr": typestr, "data": (ptr, False), "version": 2, "strides": None}
 
     return torch.as_tensor(_Holder(), device=f"cuda:{device}")
+
+
+def jackknife_selection(times, n, d):
+    """Delete-d jackknife selection [C][mtr] (int8, 1 = kept), C = binomial(n, d), from trace start times (seconds since 1970;
+    day-of-year bins, tspws_jackknife_plan).  Raises when there are no start times (times[0] == 0)."""
+    import math
+    import numpy as np
+    times = np.ascontiguousarray(times, dtype=np.int64)
+    if times.ndim != 1 or not times.size:
+        raise TspwsError("times must be a non-empty 1-D array of start times")
+    if not 0 < d < n:
+        raise TspwsError(f"jackknife needs 0 < d < n, got n = {n}, d = {d}")
+    Cn = math.comb(n, d)
+    sel = np.zeros((Cn, times.size), np.int8)
+    rc = load().tspws_jackknife_plan(sel.ctypes.data, times.ctypes.data, times.size, d, n, Cn)
+    if rc:
+        raise TspwsError("jackknife_selection: no trace start times" if rc == -2 else f"jackknife_selection failed with code {rc}")
+    return sel
+
+
+def selection_classes(sel):
+    """(class_of_trace[mtr] uint32, kept[C][ncls] int8) of a selection [C][mtr]: traces with identical selection columns form a class,
+    numbered in order of first appearance (tspws_selection_classes)."""
+    import numpy as np
+    sel = np.ascontiguousarray(sel, dtype=np.int8)
+    if sel.ndim != 2:
+        raise TspwsError("selection must be 2-D [C][mtr]")
+    Cn, mtr = sel.shape
+    cls = np.zeros(mtr, np.uint32)
+    kept = np.zeros(Cn * max(mtr, 1), np.int8)
+    n = C.c_uint()
+    check(load().tspws_selection_classes(sel.ctypes.data, Cn, mtr, cls.ctypes.data, kept.ctypes.data, C.byref(n)), "selection_classes")
+    return cls, kept[:Cn * n.value].reshape(Cn, n.value).copy()
 
 
 def synth(mtr, N, seed=0, first=0, device=0, pad=0):

@@ -71,7 +71,7 @@ static void usage(void)
 	     "  wu=2               phase-weight power            J= V= s0= b0= fmin=   frame sampling\n"
 	     "  Q= | cycles= | cyc= | w0=   Morlet shape         MexHat   complex Mexican-hat frame\n"
 	     "  rm  fold  uni  verbose  unbiased                 TwoStage[=10]   two-stage stack\n"
-	     "  jackknife_n= jackknife_d=   (TwoStage only)      obin   replicas to one msacs file\n"
+	     "  jackknife_n= jackknife_d=   delete-d replicas    obin   replicas to one msacs file\n"
 	     "  Nmax=              use the first Nmax traces     osac=X kinst=S  output naming / header\n"
 	     "  convergence[=ref.sac] AllSteps   convergence curves   subsmpl_N= subsmpl_prob=   random subsampling\n"
 	     "OUTPUT: tl[_X].sac (linear stack), ts_pws[_X].sac (ts-PWS), *_subsmpl_<m>.sac replicas.\n"

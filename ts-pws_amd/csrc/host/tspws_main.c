@@ -10,15 +10,17 @@
  * Covered: fold (:71-88), parameter resolution (:91-124), mean removal
  * (:159-169), single- and two-stage stacks (:194-242), biased / unbiased
  * weighting (:226-228), convergence curves (:247-314), random subsampling
- * (:324-333), two-stage jackknife (:335-345).
+ * (:324-333), two-stage jackknife (:335-345); beyond the reference, the
+ * single-stage jackknife (its tspws_jackknife_float is an empty stub, :711-716:
+ * tspws_hip_jackknife_single fills the replica rows).
  *
  * Several devices: TSPWS_DEVICES="0,1,2,3" (or "all") shards in->sigall by
  * traces over those devices of this process -- every device pulls its shard
  * over its own PCIe link, sums it (ts_pws1f_lib.c:866-881), ONE RCCL
  * all-reduce over xGMI adds the shards, the finish stage is split by scales
- * (include/tspws_hip.h, "several devices").  Convergence curves and random
- * subsampling need the whole ensemble on one device and take the single-
- * device path.
+ * (include/tspws_hip.h, "several devices").  Convergence curves, random
+ * subsampling and the single-stage jackknife need the whole ensemble on one
+ * device and take the single-device path.
  *
  * The frame (plan) and the device trace buffer of the last call ON EACH DEVICE
  * are kept: a caller that stacks many ensembles of the same length with the
@@ -341,10 +343,12 @@ static int run_call(t_tsPWS *tspws, t_tsPWS_out *out, t_data *in, int dev, int a
 	/* a one-entry TSPWS_DEVICES names THE device of the call (the sharded path on one device only under TSPWS_COMM: tests) */
 	if (ndev == 1 && !getenv("TSPWS_COMM")) { dev = devs[0]; ndev = 0; }
 
-	/* several devices (or TSPWS_COMM set: the sharded path even on one device -- tests); convergence curves and random subsampling
-	 * need the whole ensemble in one place: such a call runs on the FIRST device of the list, not on TSPWS_DEVICE's default */
+	/* several devices (or TSPWS_COMM set: the sharded path even on one device -- tests); convergence curves, random subsampling and
+	 * the single-stage jackknife need the whole ensemble in one place: such a call runs on the FIRST device of the list, not on TSPWS_DEVICE's default */
 	const int needs_one = (tspws->convergence && out->ls_sim && out->tsPWS_sim && out->ls_misfit && out->tsPWS_misfit) ||
-	                      (tspws->subsmpl_N > 0 && tspws->subsmpl_p > 0 && out->ls_subsmpl && out->tsPWS_subsmpl);
+	                      (tspws->subsmpl_N > 0 && tspws->subsmpl_p > 0 && out->ls_subsmpl && out->tsPWS_subsmpl) ||
+	                      (tspws->jackknife_n > 0 && tspws->jackknife_d > 0 && !(tspws->Kmax && tspws->Kmax <= mtr) && out->M && out->ls_subsmpl &&
+	                       out->tsPWS_subsmpl && out->mtr_subsmpl);
 	if (ndev >= 1) dev = devs[0];
 	if (dev < 0 || dev >= TSPWS_MAX_DEVICES || tspws_hip_device_count() <= dev) {
 		printf("tspws_main: no usable HIP device %d (%s)\n", dev, tspws_hip_last_error());
@@ -482,6 +486,29 @@ static int main_single(dev_slot *sl, t_tsPWS *tspws, t_tsPWS_out *out, t_data *i
 			} else
 				printf("tspws_main: jackknife needs trace start times (binary input); replicas left untouched.\n");
 		}
+	}
+
+	/* single-stage jackknife (an extension: the reference's variant is an empty stub, :711-716): the stack above ran unchanged, the
+	 * replicas come from per-class stacks of the same traces (include/tspws_hip.h) */
+	if (tspws->jackknife_n > 0 && tspws->jackknife_d > 0 && !(tspws->Kmax && tspws->Kmax <= mtr) && out->M && out->ls_subsmpl &&
+	    out->tsPWS_subsmpl && out->mtr_subsmpl) {
+		const unsigned C = out->M;
+		sel = (char *)calloc((size_t)C * mtr, 1);
+		jk_mtr = (unsigned *)malloc((size_t)C * sizeof(unsigned));
+		if (!sel || !jk_mtr) { rc = TSPWS_E_NOMEM; goto done; }
+		if (tspws_jackknife_plan(sel, in->time, mtr, tspws->jackknife_d, tspws->jackknife_n, C) == 0) {
+			TRY(tspws_hip_alloc((void **)&d_jk, 2 * (size_t)C * ld * sizeof(float), dev));
+			TRY(tspws_hip_jackknife_single(plan, tspws, d_sig, ld, mtr, sel, C, d_jk, d_jk + (size_t)C * ld, jk_mtr, NULL));
+			stage = (float *)malloc(2 * (size_t)C * ld * sizeof(float));
+			if (!stage) { rc = TSPWS_E_NOMEM; goto done; }
+			TRY(tspws_hip_download(stage, d_jk, 2 * (size_t)C * ld * sizeof(float), NULL));
+			for (unsigned c = 0; c < C; c++) {
+				memcpy(out->ls_subsmpl[c], stage + (size_t)c * ld, ld * sizeof(float));
+				memcpy(out->tsPWS_subsmpl[c], stage + ((size_t)C + c) * ld, ld * sizeof(float));
+				out->mtr_subsmpl[c] = jk_mtr[c];
+			}
+		} else
+			printf("tspws_main: jackknife needs trace start times (binary input); replicas left untouched.\n");
 	}
 
 done:
