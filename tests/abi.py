@@ -327,3 +327,40 @@ def read_sac(path):
     fl = np.frombuffer(raw, "<f4", 70, 0)
     it = np.frombuffer(raw, "<i4", 40, 280)
     return dict(f=fl, i=it, k=raw[440:632], data=np.frombuffer(raw, "<f4", int(it[9]), 632).copy())
+
+
+WIDE_BACKGROUNDS = (1e-8, 1e-10, 1e-11, 1e-12, 1e-14, 1e-20, 1e-30)
+
+
+def wide_traces(mtr, N, seed=0, every=1):
+    """Seeded ensemble with WIDE-DYNAMIC-RANGE traces among abi.synth_traces ones (float32 [mtr][N]).  Trace j = every * i (i = 0, 1, ..)
+    is replaced by wide trace i while there are any: a unit spike over a seeded background b * U(-1, 1) for each b in WIDE_BACKGROUNDS, then
+    a spike over an EXACTLY zero trace, a trace half zero / half 1e-13 noise with a unit-amplitude segment, a spike over float subnormals
+    (~1e-40), subnormals alone, and an ordinary trace scaled by 1e-30.  Spikes and segments sit at a different position in every trace, so
+    that the ensemble is loud where one wide trace is quiet.  (A transform-based engine sees such a trace's quiet coefficients at its
+    rounding noise; the reference counts their exact phasors, ts_pws1f_lib.c:486-494.)"""
+    X = synth_traces(mtr, N, seed=seed).astype(np.float64)
+    rng = np.random.default_rng(1000 + seed)
+    wide = []
+    for b in WIDE_BACKGROUNDS:
+        wide.append(("bg", b))
+    wide += [("bg", 0.0), ("half", 1e-13), ("bg", 1e-40), ("sub", 1e-40), ("scaled", 1e-30)]
+    rows = list(range(0, mtr, max(1, every)))[:len(wide)]
+    for i, j in enumerate(rows):
+        kind, b = wide[i]
+        pos = int((seed * 7919 + (2 * i + 1) * N // (2 * len(rows)) + 37 * i) % N)
+        u = rng.uniform(-1.0, 1.0, N)
+        if kind == "bg":
+            x = b * u
+            x[pos] = 1.0
+        elif kind == "half":
+            x = np.zeros(N)
+            x[N // 2:] = b * u[N // 2:]
+            s0 = N // 2 + pos % (N // 2 - 128)
+            x[s0: s0 + 128] = u[s0: s0 + 128]
+        elif kind == "sub":
+            x = b * u
+        else:
+            x = b * X[j]
+        X[j] = x
+    return np.ascontiguousarray(X.astype(np.float32))

@@ -8,7 +8,7 @@ these arrays -- inputs from this repo's own seeded generator, outputs from the
 reference library -- are what pins the oracle and the HIP path.
 
     python tests/golden/make_golden.py          # rewrites tests/golden/*.npz
-    python tests/golden/make_golden.py extra    # extra.npz only (synth50: ref_synth50.npz only)
+    python tests/golden/make_golden.py extra    # extra.npz only (synth50: ref_synth50.npz only, wide: ref_wide256.npz only)
 
 Fixtures are data only: inputs and expected outputs.
 """
@@ -284,8 +284,28 @@ def synth50():
     print("synth50 fixtures written")
 
 
+WIDE = dict(mtr=256, N=4096, seed=5, every=19)
+WIDE_CASES = (("morlet", dict()), ("exact_morlet_wu15", dict(type=-2, wu=1.5)), ("mexhat", dict(type=-3)))
+
+
+def wide():
+    """The reference's ls / tsPWS on one seeded wide-dynamic-range ensemble, abi.wide_traces(**WIDE) (spikes over backgrounds 8 .. 40
+    decades below them, exact zeros, subnormals -- regenerated by the tests, so only the outputs are stored): what
+    tests/test_wide_range_cpu.py holds the oracle and tests/test_phase_skip_gpu.py holds tspws_main to."""
+    lib = ref_lib()
+    X = abi.wide_traces(**WIDE)
+    ex = {k: np.int64(v) for k, v in WIDE.items()}
+    for name, kw in WIDE_CASES:
+        abi.srand(1)
+        r = abi.run_main(lib.tspws_main, abi.default_params(**kw), X)
+        assert r["rc"] == 0, (name, r["rc"])
+        ex.update({f"{name}/ls": r["ls"], f"{name}/tsPWS": r["tsPWS"]})
+    np.savez_compressed(os.path.join(HERE, "ref_wide256.npz"), **ex)
+    print("wide fixtures written")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] in ("extra", "synth50"):
-        {"extra": extra, "synth50": synth50}[sys.argv[1]]()
+    if len(sys.argv) > 1 and sys.argv[1] in ("extra", "synth50", "wide"):
+        {"extra": extra, "synth50": synth50, "wide": wide}[sys.argv[1]]()
     else:
         main()

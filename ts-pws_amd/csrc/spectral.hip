@@ -593,16 +593,28 @@ __global__ void __launch_bounds__(256) k_spec_fold_mfma(const double2 *__restric
 }
 
 // ---- inverse transforms of the folded spectra + stacks -----------------------------------------------------------------------------
+// Phase stack near the noise floor.  An output of the transforms is off by at most fl = tau max|x_t| (tau: spec_build's tau_of), so its phase
+// is only known where |y| is well above fl.  A trace that is quiet at a coefficient while the ensemble is not (a spike over a background 12 or
+// more decades below it, a dead channel with one glitch) has |y| near or below fl there, yet the reference counts the phasor of its exact
+// FIR sum (ts_pws1f_lib.c:486-494).  So the phasor comes from the transform only above SPEC_EXACT_G fl; below, from the exact FP64 sum
+// (k_spec_fixup, k_spec_stack_rows).  With 2^10 the phase error of a transform phasor that is kept is below 1e-3 rad even at the bound tau
+// itself; FP64 transforms of spike-over-background traces are off by ~5e-5 fl, some 1e4 times less.  The linear stack ST keeps the transform's
+// value everywhere: its absolute error stays below fl.  Real data sits far above the threshold (the shipped example: >= 1e6 fl), where
+// nothing changes.
+#define SPEC_EXACT_G 1024.0
+
 // A segment = one pass of one scale.  Passes before the last write the other ping-pong buffer; the last pass conjugates
 // (Y = conj r), phase-normalises and adds the block's 64 traces into the block's ST / PS planes (COEF: writes the traces' own
 // coefficients instead -- the per-trace API and the parity tests).
 struct SpecEpi {
 	double2 *ST, *PS;          // planes of trace block 0; block tb at + tb * stride
 	size_t stride;
-	const unsigned *amax;      // float bits of max |x| per trace (lane)
+	const double *amax;        // max |x| per trace (lane)
 	double2 *Y;                // COEF: [trace][ncoef]
 	size_t ncoef;
 	unsigned ntr;
+	unsigned long long *mask;  // stacks: [trace block][spectral coefficient] words of the lanes left to k_spec_fixup
+	unsigned long long nspec, coff0; // spectral coefficients of a block; coefficient index of the first one
 };
 
 template <int R, bool COEF>
@@ -623,10 +635,14 @@ __device__ __forceinline__ void spec_inv_last_body(const double2 *__restrict__ s
 		}
 		return;
 	}
-	// noise floor of the transforms for this (trace, scale): a coefficient at or below it is an exact zero of the FIR form (all samples
-	// under the filter are zero) and is skipped by the phase stack like the reference's 0 / 0 (ts_pws1f_lib.c:491-492)
-	const double fl = sg->tau * (double)__uint_as_float(ep.amax[t]);
-	const double fl2 = fl * fl;
+	// noise floor of the transforms for this (trace, scale), fl = tau max|x_t|: the phasor of a coefficient at or below SPEC_EXACT_G fl is not taken
+	// from the transform (its phase may be noise); the lane sets its bit in the block's mask word instead and k_spec_fixup adds the phasor of the
+	// exact FP64 sum (an exact zero -- all samples under the filter zero -- adds nothing, like the reference's 0 / 0, ts_pws1f_lib.c:491-492).
+	// An all-zero trace (nothing to add) or a non-finite one sets no bits.
+	const double am = ep.amax[t];
+	const double thr = SPEC_EXACT_G * sg->tau * am, thr2 = thr * thr;
+	const bool exact_ok = am > 0.0 && am <= 1.7976931348623157e308;
+	unsigned long long *mrow = ep.mask + (size_t)tb * ep.nspec + (sg->coff - ep.coff0);
 	const unsigned o16 = ((lane >> 5) & 1) * 8 + ((lane >> 4) & 1) * 4 + ((lane >> 3) & 1) * 2 + ((lane >> 2) & 1); // element left by valu_reduce16
 	double2 *pS = ep.ST + (size_t)tb * ep.stride + sg->coff, *pP = ep.PS + (size_t)tb * ep.stride + sg->coff;
 	constexpr int NCH = (R + 7) / 8;
@@ -641,7 +657,11 @@ __device__ __forceinline__ void spec_inv_last_body(const double2 *__restrict__ s
 			if (n < R) {
 				y = make_double2(v[n < R ? n : 0].x, -v[n < R ? n : 0].y);
 				const double r2 = fma(y.x, y.x, y.y * y.y);
-				if (r2 > fl2) add_unit_phasor(u, y);
+				const bool counted = r2 > thr2;
+				if (counted) add_unit_phasor(u, y);
+				const unsigned long long word = __ballot(!counted && exact_ok); // (written for every coefficient: no clearing pass)
+				const size_t kk = j0 + (size_t)n * L;
+				if (lane == 0 && kk < sg->nvalid) mrow[kk] = word;
 			}
 			st16[2 * i] = y.x; st16[2 * i + 1] = y.y;
 			ps16[2 * i] = u.x; ps16[2 * i + 1] = u.y;
@@ -698,7 +718,78 @@ struct SpecRowScale {
 	unsigned long long coff;   // first coefficient of the scale in a coefficient set
 	double tau;
 	unsigned Ns, buf;          // buf: which of the two buffers the scale's last pass wrote
+	unsigned s, pad;           // the scale itself (its taps: spec_fir_exact)
 };
+
+// the scale of spectral coefficient i: the last one with roff <= i (rs[0].roff = 0) -- counted by the lanes (a binary search is five DEPENDENT
+// loads; at most 128 spectral scales)
+__device__ __forceinline__ unsigned spec_row_scale(const SpecRowScale *__restrict__ rs, unsigned nrs, unsigned lane, unsigned long long i)
+{
+	const unsigned long long ro0 = lane < nrs ? rs[lane].roff : ~0ull, ro1 = lane + 64 < nrs ? rs[lane + 64].roff : ~0ull;
+	return (unsigned)__popcll(__ballot(ro0 <= i)) + (unsigned)__popcll(__ballot(ro1 <= i)) - 1u;
+}
+
+// r_s[k D] = sum_l x[(k D - c + l) mod N] w_s[l] of one trace / row in FP64 (the FIR form of cdotx.c:44-70, the oracle's orc_forward); col = the
+// lane's column of the transposed batch ([N][TP]).  Only for coefficients within SPEC_EXACT_G of the noise floor: L loads per coefficient.
+template <typename TIn>
+__device__ __forceinline__ double2 spec_fir_exact(const TIn *__restrict__ col, unsigned TP, unsigned N, const ScaleDesc &d, const double2 *__restrict__ w, unsigned k)
+{
+	long long n0 = ((long long)k * d.D - d.c) % (long long)N;
+	const unsigned n = (unsigned)(n0 < 0 ? n0 + N : n0), l0 = min(d.L, N - n); // the window wraps at most once (L <= N)
+	const double2 *__restrict__ ws = w + d.tap_off;
+	const TIn *__restrict__ xp = col + (size_t)n * TP;
+	double2 a = make_double2(0.0, 0.0);
+#pragma unroll 8
+	for (unsigned l = 0; l < l0; l++) { // (unrolled: eight rows in flight)
+		const double x = (double)xp[(size_t)l * TP];
+		a.x = fma(x, ws[l].x, a.x);
+		a.y = fma(x, ws[l].y, a.y);
+	}
+#pragma unroll 8
+	for (unsigned l = l0; l < d.L; l++) {
+		const double x = (double)col[(size_t)(l - l0) * TP];
+		a.x = fma(x, ws[l].x, a.x);
+		a.y = fma(x, ws[l].y, a.y);
+	}
+	return a;
+}
+
+// ---- exact phasors of the coefficients within SPEC_EXACT_G of the noise floor (per-trace stacks) ------------------------------------------------
+// A wave takes 64 spectral coefficients of one trace block; for each one whose mask word (k_spec_inv) is non-zero, the lanes of the set bits
+// compute the exact FP64 sum, and the phasors are added in trace order to the block's PS entry.  One writer per entry, no atomics.
+template <typename TIn>
+__global__ void __launch_bounds__(256) k_spec_fixup(const unsigned long long *__restrict__ mask, unsigned long long nspec, const SpecRowScale *__restrict__ rs,
+                                                    unsigned nrs, const ScaleDesc *__restrict__ sc, const double2 *__restrict__ w, const TIn *__restrict__ xT,
+                                                    unsigned TP, unsigned N, double2 *__restrict__ PS, size_t stride)
+{
+	const unsigned lane = threadIdx.x & 63, wv = threadIdx.x >> 6, tb = blockIdx.y;
+	const unsigned long long i0 = ((unsigned long long)blockIdx.x * 4 + wv) * 64;
+	if (i0 >= nspec) return;
+	const unsigned long long mine = i0 + lane < nspec ? mask[(size_t)tb * nspec + i0 + lane] : 0ull;
+	for (unsigned long long todo = __ballot(mine != 0ull); todo; todo &= todo - 1) {
+		const unsigned j = (unsigned)__builtin_ctzll(todo);
+		const unsigned long long word = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(mine >> 32), (int)j) << 32) |
+		                                (unsigned)__builtin_amdgcn_readlane((int)(unsigned)mine, (int)j);
+		const unsigned long long i = i0 + j;
+		const SpecRowScale d = rs[spec_row_scale(rs, nrs, lane, i)];
+		const ScaleDesc sd = sc[d.s];
+		const unsigned k = (unsigned)(i - d.roff);
+		double2 u = make_double2(0.0, 0.0);
+		if ((word >> lane) & 1ull) {
+			const double2 r = spec_fir_exact<TIn>(xT + (size_t)tb * 64 + lane, TP, N, sd, w, k);
+			add_unit_phasor(u, make_double2(r.x, -r.y)); // Y = conj r
+		}
+		double2 *pp = PS + (size_t)tb * stride + d.coff + k;
+		double2 ps = *pp;
+		for (unsigned long long b = word; b; b &= b - 1) { // (trace order)
+			const int l = __builtin_ctzll(b);
+			ps.x += __shfl(u.x, l, 64);
+			ps.y += __shfl(u.y, l, 64);
+		}
+		if (lane == 0) *pp = ps;
+	}
+}
+
 struct SpecRowsOut {
 	double2 *OUT; size_t out_stride; const double *Mv; double M, K, wu; int mode, keep; double2 *keepST; // weighted sets (OUT != NULL) ...
 	double2 *accST, *accPS; size_t stride;                                                                 // ... or plane pairs per column
@@ -706,17 +797,14 @@ struct SpecRowsOut {
 
 __global__ void __launch_bounds__(256) k_spec_stack_rows(const SpecRowScale *__restrict__ rs, unsigned nrs, unsigned long long ntot, const double2 *__restrict__ b0,
                                                          size_t rows0, const double2 *__restrict__ b1, size_t rows1, unsigned nblk, unsigned ntr, unsigned tps,
-                                                         unsigned ncol, const unsigned *__restrict__ amax, const SpecRowsOut o)
+                                                         unsigned ncol, const double *__restrict__ amax, const ScaleDesc *__restrict__ sc, const double2 *__restrict__ taps,
+                                                         const double *__restrict__ xT, unsigned N, const SpecRowsOut o)
 {
 	extern __shared__ double slab[]; // [4 waves][nblk 64 lanes][4]
 	const unsigned lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 	const unsigned long long i = (unsigned long long)blockIdx.x * 4 + wv;
 	if (i >= ntot) return;
-	// the scale of coefficient i: the last one with roff <= i (rs[0].roff = 0) -- counted by the lanes (a binary search is five DEPENDENT loads;
-	// at most 128 spectral scales)
-	const unsigned long long ro0 = lane < nrs ? rs[lane].roff : ~0ull, ro1 = lane + 64 < nrs ? rs[lane + 64].roff : ~0ull;
-	const unsigned lo = (unsigned)__popcll(__ballot(ro0 <= i)) + (unsigned)__popcll(__ballot(ro1 <= i)) - 1u;
-	const SpecRowScale d = rs[lo];
+	const SpecRowScale d = rs[spec_row_scale(rs, nrs, lane, i)];
 	const size_t k = (size_t)(i - d.roff);
 	const double2 *__restrict__ src = d.buf ? b1 : b0;
 	const size_t rows = d.buf ? rows1 : rows0;
@@ -726,8 +814,13 @@ __global__ void __launch_bounds__(256) k_spec_stack_rows(const SpecRowScale *__r
 		const double2 r = src[((size_t)tb * rows + d.goff + k) * 64 + lane];
 		const double2 y = t < ntr ? make_double2(r.x, -r.y) : make_double2(0.0, 0.0); // Y = conj r
 		double2 u = make_double2(0.0, 0.0);
-		const double fl = d.tau * (double)__uint_as_float(amax[t]);
-		if (fma(y.x, y.x, y.y * y.y) > fl * fl) add_unit_phasor(u, y);               // (at or below the transforms' noise floor: an exact zero of the FIR form)
+		// within SPEC_EXACT_G of the transforms' noise floor (k_spec_inv): the phasor of the exact FP64 sum, computed here by the lanes concerned
+		const double am = amax[t], thr = SPEC_EXACT_G * d.tau * am;
+		if (fma(y.x, y.x, y.y * y.y) > thr * thr) add_unit_phasor(u, y);
+		else if (t < ntr && am > 0.0 && am <= 1.7976931348623157e308) {
+			const double2 ex = spec_fir_exact<double>(xT + t, nblk * 64, N, sc[d.s], taps, (unsigned)k);
+			add_unit_phasor(u, make_double2(ex.x, -ex.y));
+		}
 		double *e = w + (size_t)t * 4;
 		e[0] = y.x; e[1] = y.y; e[2] = u.x; e[3] = u.y;
 	}
@@ -1004,6 +1097,7 @@ static int spec_build(tspws_hip_plan *p, unsigned s_first, unsigned nblk_hint, S
 				q.roff = ro; q.goff = goff[s]; q.coff = p->sc[s].coef_off; q.Ns = Ns;
 				q.buf = (unsigned)(radix_bits(ilog2u(N / p->sc[s].D), 4).size() & 1u);
 				q.tau = tau_of(s);
+				q.s = s;
 				rv.push_back(q);
 				ro += Ns;
 			}
@@ -1098,8 +1192,13 @@ static int spectral_run(tspws_hip_plan *p, SpecDecomp *dc, const TIn *xT, unsign
 	double2 *B = (double2 *)v;
 	if ((rc = scratch(p, SCR_SPG, (size_t)nblk * sp->grows * 64 * sizeof(double2), &v))) return rc;
 	double2 *G = (double2 *)v;
-	if ((rc = scratch(p, SCR_SPM, (size_t)TP * sizeof(unsigned), &v))) return rc;
-	unsigned *amax = (unsigned *)v;
+	if ((rc = scratch(p, SCR_SPM, (size_t)TP * sizeof(double), &v))) return rc;
+	const double *amax = (const double *)v;
+	unsigned long long *mask = nullptr; // [nblk][spectral coefficients]: lanes whose phasor k_spec_fixup adds (stacks of a per-trace batch)
+	if (!Y && !ro) {
+		if ((rc = scratch(p, SCR_SPK, (size_t)nblk * sp->nrowcoef * sizeof(unsigned long long), &v))) return rc;
+		mask = (unsigned long long *)v;
+	}
 	// (amax: the largest |sample| of every trace / row, left there by the transposition -- tspws_spectral_transpose_*, spectral_rows)
 	// trace transform
 	const size_t np = sp->fwd_bits.size();
@@ -1146,6 +1245,7 @@ static int spectral_run(tspws_hip_plan *p, SpecDecomp *dc, const TIn *xT, unsign
 	// inverse transforms: ping-pong between the folded spectra and the (now free) trace-transform buffer that does not hold Xh
 	SpecEpi ep;
 	ep.ST = ST; ep.PS = PS; ep.stride = stride; ep.amax = amax; ep.Y = Y; ep.ncoef = p->ncoef; ep.ntr = ntr;
+	ep.mask = mask; ep.nspec = sp->nrowcoef; ep.coff0 = p->sc[sp->s_first].coef_off;
 	double2 *g2 = oth; // rows: xrows >= grows?  not in general: own buffer when it is too small
 	size_t g2rows = xrows;
 	if ((ro || sp->d_iseg.size() > 1) && sp->grows > xrows) {
@@ -1172,7 +1272,12 @@ static int spectral_run(tspws_hip_plan *p, SpecDecomp *dc, const TIn *xT, unsign
 		if (nblk > 8) return fail(TSPWS_E_ARG, "spectral: at most 512 rows in columns");
 		const size_t lds = (size_t)4 * nblk * 64 * 4 * sizeof(double);
 		hipLaunchKernelGGL(k_spec_stack_rows, dim3((unsigned)((sp->nrowcoef + 3) / 4)), dim3(256), lds, st, (const SpecRowScale *)sp->d_rows, sp->s_end - sp->s_first, sp->nrowcoef,
-		                   (const double2 *)G, sp->grows, (const double2 *)g2, g2rows, nblk, ntr, tps, ncol, (const unsigned *)amax, *ro);
+		                   (const double2 *)G, sp->grows, (const double2 *)g2, g2rows, nblk, ntr, tps, ncol, amax, (const ScaleDesc *)p->d_sc, (const double2 *)p->d_w,
+		                   (const double *)xT, sp->Nx, *ro);
+	} else if (mask) {
+		const unsigned nw = (unsigned)((sp->nrowcoef + 63) / 64);
+		hipLaunchKernelGGL((k_spec_fixup<TIn>), dim3((nw + 3) / 4, nblk), dim3(256), 0, st, (const unsigned long long *)mask, (unsigned long long)sp->nrowcoef,
+		                   (const SpecRowScale *)sp->d_rows, sp->s_end - sp->s_first, (const ScaleDesc *)p->d_sc, (const double2 *)p->d_w, xT, TP, sp->Nx, PS, stride);
 	}
 	HIP_TRY(hipGetLastError());
 	return 0;
@@ -1182,7 +1287,7 @@ static int spectral_run(tspws_hip_plan *p, SpecDecomp *dc, const TIn *xT, unsign
 // sets or plane pairs per column (SpecRowsOut); d_x: the rows themselves ([ntr][ld]), transposed here.
 #define SPEC_TR_TILES 4 /* 64-sample tiles per workgroup of the rows transposition */
 template <typename TIn> __global__ void __launch_bounds__(256) k_spec_transpose_rows(const TIn *__restrict__ x, size_t ld, unsigned ntr, unsigned N, unsigned TP,
-                                                                                      TIn *__restrict__ xT, unsigned *__restrict__ pmax)
+                                                                                      TIn *__restrict__ xT, unsigned long long *__restrict__ pmax)
 {
 	// a workgroup transposes SPEC_TR_TILES tiles of 64 rows x 64 samples and keeps the rows' largest |sample| on the way (the noise floor of the
 	// transforms scales with it): written per workgroup to pmax[blockIdx.x][TP], reduced by k_spec_rowmax.  (Atomics on the rows' maxima: one per
@@ -1191,9 +1296,9 @@ template <typename TIn> __global__ void __launch_bounds__(256) k_spec_transpose_
 	__shared__ TIn tile[64][65];
 	const unsigned t0 = blockIdx.y * 64;
 	const unsigned tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-	float m[16];
+	TIn m[16]; // (in the rows' own precision: a double row may lie below the float range)
 #pragma unroll
-	for (int i = 0; i < 16; i++) m[i] = 0.f;
+	for (int i = 0; i < 16; i++) m[i] = (TIn)0;
 	for (unsigned it = 0; it < SPEC_TR_TILES; it++) {
 		const unsigned n0 = (blockIdx.x * SPEC_TR_TILES + it) * 64;
 		if (n0 >= N) break;
@@ -1207,8 +1312,8 @@ template <typename TIn> __global__ void __launch_bounds__(256) k_spec_transpose_
 #pragma unroll
 		for (int i = 0; i < 16; i++) {
 			tile[ty + 4 * i][tx] = v[i];
-			const float a = fabsf((float)v[i]);
-			m[i] = (a == a) ? fmaxf(m[i], a) : __int_as_float(0x7f800000);
+			const TIn a = v[i] < (TIn)0 ? -v[i] : v[i];
+			m[i] = (a == a) ? (a > m[i] ? a : m[i]) : (TIn)INFINITY;
 		}
 		__syncthreads();
 #pragma unroll
@@ -1216,19 +1321,19 @@ template <typename TIn> __global__ void __launch_bounds__(256) k_spec_transpose_
 	}
 #pragma unroll
 	for (int i = 0; i < 16; i++) {
-		float a = m[i];
+		double a = (double)m[i];
 #pragma unroll
-		for (int o = 32; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
-		if (tx == 0) pmax[(size_t)blockIdx.x * TP + t0 + ty + 4u * (unsigned)i] = __float_as_uint(a * 1.0000002f); // (non-negative floats order like their bit patterns)
+		for (int o = 32; o > 0; o >>= 1) a = fmax(a, __shfl_xor(a, o, 64));
+		if (tx == 0) pmax[(size_t)blockIdx.x * TP + t0 + ty + 4u * (unsigned)i] = (unsigned long long)__double_as_longlong(a); // (non-negative doubles order like their bit patterns)
 	}
 }
 
 // amax[t] = max over the np workgroup rows of pmax[.][t]; grid = TP / 64 blocks of 1024 threads (16 waves share the rows, lane = trace)
-__global__ void __launch_bounds__(1024) k_spec_rowmax(const unsigned *__restrict__ pmax, unsigned np, unsigned TP, unsigned *__restrict__ amax)
+__global__ void __launch_bounds__(1024) k_spec_rowmax(const unsigned long long *__restrict__ pmax, unsigned np, unsigned TP, unsigned long long *__restrict__ amax)
 {
-	__shared__ unsigned sm[16][64];
+	__shared__ unsigned long long sm[16][64];
 	const unsigned lane = threadIdx.x & 63, wv = threadIdx.x >> 6, t = blockIdx.x * 64 + lane;
-	unsigned a = 0;
+	unsigned long long a = 0;
 	for (unsigned g = wv; g < np; g += 16) a = max(a, pmax[(size_t)g * TP + t]);
 	sm[wv][lane] = a;
 	__syncthreads();
@@ -1248,10 +1353,10 @@ static int spectral_transpose(tspws_hip_plan *p, const TIn *d_x, size_t ld, unsi
 	const unsigned nblk = TP / 64;
 	void *v;
 	const unsigned np = (p->N + 64 * SPEC_TR_TILES - 1) / (64 * SPEC_TR_TILES);
-	if (int rc = scratch(p, SCR_SPM, (size_t)TP * (np + 1) * sizeof(unsigned), &v)) return rc;
-	unsigned *amax = (unsigned *)v, *pmax = amax + TP;
+	if (int rc = scratch(p, SCR_SPM, (size_t)TP * (np + 1) * sizeof(double), &v)) return rc;
+	unsigned long long *amax = (unsigned long long *)v, *pmax = amax + TP;
 	hipLaunchKernelGGL((k_spec_transpose_rows<TIn>), dim3(np, nblk), dim3(256), 0, st, d_x, ld, ntr, p->N, TP, xT, pmax);
-	hipLaunchKernelGGL(k_spec_rowmax, dim3(nblk), dim3(1024), 0, st, (const unsigned *)pmax, np, TP, amax);
+	hipLaunchKernelGGL(k_spec_rowmax, dim3(nblk), dim3(1024), 0, st, (const unsigned long long *)pmax, np, TP, amax);
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
