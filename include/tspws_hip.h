@@ -169,6 +169,28 @@ int  tspws_hip_stack_finish_tail(tspws_hip_plan *plan, const t_tsPWS *p, size_t 
 /* Single-GPU convenience: _local + _finish in one call; on return all work is ordered on `stream`. */
 int  tspws_hip_stack(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, size_t mtr,
                      float *d_ls, float *d_tsPWS, void *stream);
+/* B ensembles of the same trace length, one stack each.  Ensemble b is the traces [h_first[b], h_first[b+1]) of d_sigall (h_first has
+ * B + 1 non-decreasing host entries, h_first[0] may be > 0).  Row b of d_ls / d_tsPWS ([B][max] floats) receives what
+ * tspws_hip_stack(plan, p, d_sigall + h_first[b] * ld, ld, h_first[b+1] - h_first[b], ...) would write, to the parity tolerance (relerr
+ * 2e-6; a call with B = 1 IS that call).  Every ensemble follows the single call's rules: two-stage iff 0 < Kmax <= M_b
+ * (tspws_is_two_stage), weights with K = M = M_b (single-stage) or (Kmax, M_b), ls divided by M_b; a batch may mix both kinds.  An empty
+ * ensemble (M_b = 0) gives zero rows.  Fold and mean removal stay with the caller (tspws_hip_fold / tspws_hip_remove_mean on the whole
+ * array).  The single-stage ensembles go through ONE many-trace pass when their total trace count takes that path (each ensemble starts a
+ * fresh 64-trace block), the two-stage ensembles through one streaming pass and one few-row finish.  Every scratch block that grows with
+ * the ensembles stays within TSPWS_PART_MB (ensembles are processed in rounds).  NULL pointers, decreasing offsets or ld < max return TSPWS_E_ARG before any device work; B = 0
+ * returns 0 and does nothing.  The call waits for `stream`: on return the outputs are complete. */
+int  tspws_hip_stack_batch(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, const size_t *h_first, unsigned B,
+                           float *d_ls, float *d_tsPWS, void *stream);
+/* How the ensembles of the plan's last tspws_hip_stack_batch call with B > 0 were stacked (all zero before the first one). */
+typedef struct {
+	unsigned single_pass;    /* single-stage ensembles stacked by the shared many-trace pass                               */
+	unsigned two_stage_pass; /* two-stage ensembles stacked by the shared streaming pass and few-row finish                */
+	unsigned looped;         /* ensembles stacked by one tspws_hip_stack each (below the many-trace rule / alone of their kind) */
+	unsigned empty;          /* ensembles without traces (zero rows)                                                      */
+	unsigned rounds;         /* rounds of the two shared passes (scratch budget; a round never splits an ensemble)        */
+	unsigned pass_batches;   /* batches of the many-trace pass (an ensemble may straddle two)                             */
+} tspws_hip_batch_stats;
+int  tspws_hip_stack_batch_stats(const tspws_hip_plan *plan, tspws_hip_batch_stats *stats);
 /* Optional timing inside tspws_hip_stack: HIP events on `stream` at the start of the call, after its streaming stage (the
  * partial-stack launches) and at its end, for up to max_calls calls.  _read synchronises the device and returns the per-call
  * durations in ms (either array may be NULL; *ncalls = calls recorded); _end returns the mean of the streaming stage and

@@ -107,6 +107,8 @@ SYMBOLS = {
     "tspws_hip_stack_finish_range": (_i, [_vp, _vp, _sz, _u, _u, _vp]),
     "tspws_hip_stack_finish_tail": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "tspws_hip_stack": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    "tspws_hip_stack_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _vp, _vp, _vp]),
+    "tspws_hip_stack_batch_stats": (_i, [_vp, _vp]),
     "tspws_hip_profile_begin": (_i, [_vp, _sz]),
     "tspws_hip_profile_read": (_i, [_vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "tspws_hip_profile_end": (_i, [_vp, C.POINTER(_d), C.POINTER(_sz)]),
@@ -418,6 +420,36 @@ class Plan:
         check(self.lib.tspws_hip_stack(self.h, C.byref(self.params), traces.data_ptr(), ld, mtr, self._out(ls, "ls"), self._out(ts, "ts"),
                                        self._stream()), "stack")
         return ls, ts
+
+    def stack_batch(self, traces, first, ls=None, ts=None):
+        """B ensembles of one trace array in ONE call (tspws_hip_stack_batch): ensemble b = rows [first[b], first[b+1]) of the float32
+        [mtr][N] device tensor `traces`; `first` = B + 1 non-decreasing integer offsets (first[0] may be > 0).  Returns ls[B][N], ts[B][N]
+        (float32 cuda): row b = what stack_single gives for ensemble b (an empty ensemble: zero rows)."""
+        import numpy as np
+        import torch
+        mtr, ld = self._traces(traces)
+        f = np.asarray(first)
+        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
+            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
+        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
+            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
+        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
+        B = f.size - 1
+        ls = torch.empty((B, self.N), dtype=torch.float32, device=traces.device) if ls is None else ls
+        ts = torch.empty((B, self.N), dtype=torch.float32, device=traces.device) if ts is None else ts
+        for t, name in ((ls, "ls"), (ts, "ts")):
+            if t.dtype != torch.float32 or tuple(t.shape) != (B, self.N) or not t.is_contiguous() or not t.is_cuda or \
+                    (t.device.index or 0) != self.device:
+                raise TspwsError(f"{name} must be a contiguous float32 [{B}][{self.N}] tensor on cuda:{self.device}")
+        check(self.lib.tspws_hip_stack_batch(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, ls.data_ptr(), ts.data_ptr(),
+                                             self._stream()), "stack_batch")
+        return ls, ts
+
+    def batch_stats(self):
+        """How the last stack_batch call with B > 0 stacked its ensembles (tspws_hip_stack_batch_stats): dict of counts."""
+        st = (C.c_uint * 6)()
+        check(self.lib.tspws_hip_stack_batch_stats(self.h, C.byref(st)), "stack_batch_stats")
+        return dict(zip(("single_pass", "two_stage_pass", "looped", "empty", "rounds", "pass_batches"), list(st)))
 
     def close(self):
         if getattr(self, "h", None):

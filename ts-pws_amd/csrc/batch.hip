@@ -1,0 +1,317 @@
+// batch.hip -- many ensembles of the same trace length in one call (tspws_hip_stack_batch).
+// Reference citations are relative to the reference project's src/ directory.
+//
+// The reference stacks one ensemble per run; its workload is many station pairs, each a small ensemble of daily correlations.  One call
+// per small ensemble is a handful of launches of 5-40 us that never reach the engines that fill the GPU.  This unit stacks B ensembles
+// [first[b], first[b+1]) of one trace array in one call, every ensemble by the rules of tspws_hip_stack (stage rule, weights, epilogue):
+//   single-stage  the ensembles' traces go through ONE many-trace pass (forward.hip: tl_pass_*, engine by the TOTAL trace count):
+//                 every ensemble starts a fresh 64-trace block, its traces are gathered into the first lanes of its blocks
+//                 (k_batch_gather; idle lanes are zero traces, which add nothing to either stack), the pass leaves one plane pair per
+//                 block and per-trace partials, and k_accumulate_parts adds each ensemble's blocks / traces into its own ST / PS and
+//                 writes its weighted coefficients with K = M = M_b (runs of equal-sized ensembles share a launch: grid.y).
+//                 An ensemble that straddles two batches of the pass keeps accumulating (zero_first on its first segment only).
+//   two-stage     ONE streaming pass writes the Kmax partial-stack rows of every ensemble (tspws_run_chunks over a table of row ranges:
+//                 row (b, g) = the traces i of ensemble b with floor(i Kmax / M_b) == g, partial_linear_stacks :866-881); the rows
+//                 go through the few-trace forward kernels as one batch and k_accumulate_parts stacks each ensemble's Kmax rows
+//                 (grid.y = ensemble, weights with K = Kmax and the ensemble's own M_b).
+//   finish        per round of stacks: one batched tspws_hip_inverse of the (OUT, ST) pairs, k_batch_epilogue with each row's M_b.
+// Rounds keep every scratch block whose size grows with the ensembles -- per-stack sets, reconstructions, the inverse's octave buffer, the
+// rows, their partials and the streaming pass's chunk sums -- within the parts budget (TSPWS_PART_MB); a round never splits an ensemble.
+// Batches that the many-trace rule would not take as a whole, and a batch with a single ensemble of its kind, fall back to one
+// tspws_hip_stack per ensemble.  tspws_hip_stack_batch_stats tells which way the last call's ensembles went.
+#include "tspws_internal.h"
+
+#define is_two_stage tspws_is_two_stage
+
+// slot j of a gathered batch = trace src[j] of x (row stride ld); src[j] < 0: an idle lane of an ensemble's last block (zeros)
+__global__ void __launch_bounds__(256) k_batch_gather(const float *__restrict__ x, size_t ld, const long long *__restrict__ src, unsigned N,
+                                                      float *__restrict__ xg)
+{
+	const unsigned n = blockIdx.x * 256 + threadIdx.x;
+	if (n >= N) return;
+	const long long t = src[blockIdx.y];
+	xg[(size_t)blockIdx.y * N + n] = t >= 0 ? x[(size_t)t * ld + n] : 0.f;
+}
+
+// k_epilogue for a round of stacks: rows 2j / 2j + 1 of x are ICWT(OUT) / ICWT(ST) of stack j = blockIdx.y; its outputs go to row[j] of
+// ls / ts, ls by a FLOAT division by the stack's trace count (ts_pws1f_lib.c:233-241)
+__global__ void __launch_bounds__(256) k_batch_epilogue(const double *__restrict__ x, size_t N, const unsigned *__restrict__ row,
+                                                        const unsigned *__restrict__ cnt, float *__restrict__ ls, float *__restrict__ ts)
+{
+	const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (n >= N) return;
+	const unsigned j = blockIdx.y;
+	const size_t o = (size_t)row[j] * N + n;
+	ls[o] = (float)x[(2 * (size_t)j + 1) * N + n] / (float)cnt[j];
+	ts[o] = (float)x[2 * (size_t)j * N + n];
+}
+
+namespace {
+
+// host sources of a call's uploads: alive until its final synchronisation (a copy from pageable memory may still read them after
+// hipMemcpyAsync has returned)
+struct HostTables {
+	std::vector<char> blob;
+	std::vector<std::vector<Chunk>> chunks;
+	std::vector<std::vector<unsigned>> row_first;
+};
+
+// stacks of one round: [nr][OUT | ST] (the inverse's rows) and [nr][PS | unused] (ST and PS of a stack share one stride), reconstructions
+struct RoundBufs { double2 *Y, *PS; double *x; };
+
+int round_bufs(tspws_hip_plan *pl, size_t nr, RoundBufs *b)
+{
+	const size_t nc = pl->ncoef;
+	void *v;
+	int rc;
+	if ((rc = scratch(pl, SCR_BY, 4 * nr * nc * sizeof(double2), &v))) return rc;
+	b->Y = (double2 *)v; b->PS = b->Y + 2 * nr * nc;
+	if ((rc = scratch(pl, SCR_BX, 2 * nr * (size_t)pl->N * sizeof(double), &v))) return rc;
+	b->x = (double *)v;
+	return 0;
+}
+
+// stacks per round: every per-stack scratch block within the parts budget -- the sets (SCR_BY), the reconstructions (SCR_BX), the inverse's
+// octave buffer (SCR_OBUF: a 2 N slot per octave item, + 1 for the generic scales) and `extra` bytes per stack of the caller's own --, at
+// most 65535 (grid.y)
+size_t round_size(const tspws_hip_plan *pl, size_t n, size_t extra)
+{
+	const size_t sets = 4 * pl->ncoef * sizeof(double2), x = 2 * (size_t)pl->N * sizeof(double), obuf = (size_t)(pl->inv_noct + 1) * x;
+	const size_t r = tspws_part_budget_bytes() / std::max({sets, x, obuf, extra});
+	return std::max<size_t>(1, std::min<size_t>({r, n, 65535}));
+}
+
+// inverses + epilogue of stacks [j0, j0 + nr) of a list whose output rows / trace counts are the device tables d_row / d_cnt
+int round_finish(tspws_hip_plan *pl, const RoundBufs &b, unsigned nr, const unsigned *d_row, const unsigned *d_cnt, float *d_ls, float *d_ts, hipStream_t st)
+{
+	int rc;
+	if ((rc = tspws_hip_inverse(pl, (const double *)b.Y, 2 * (size_t)nr, b.x, (void *)st))) return rc;
+	hipLaunchKernelGGL(k_batch_epilogue, dim3((pl->N + 255) / 256, nr), dim3(256), 0, st, (const double *)b.x, (size_t)pl->N, d_row, d_cnt, d_ls, d_ts);
+	return 0;
+}
+
+// Single-stage ensembles `ens` (all with traces) through one many-trace pass.
+int batch_single(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *first, const std::vector<unsigned> &ens,
+                 size_t total, float *d_ls, float *d_ts, hipStream_t st, HostTables &keep)
+{
+	const size_t N = pl->N, nc = pl->ncoef, n = ens.size();
+	int rc;
+	void *v;
+	std::vector<char> &keep_alive = keep.blob;
+	// block layout of every ensemble (the whole call), the gather table of its slots, output rows and trace counts
+	std::vector<size_t> blk0(n + 1);
+	for (size_t j = 0; j < n; j++) blk0[j + 1] = blk0[j] + (first[ens[j] + 1] - first[ens[j]] + 63) / 64;
+	const size_t nslots = blk0[n] * 64;
+	const size_t o_row = nslots * sizeof(long long), o_cnt = o_row + n * sizeof(unsigned), bytes = o_cnt + n * sizeof(unsigned);
+	keep_alive.assign(bytes, 0);
+	long long *src = (long long *)keep_alive.data();
+	unsigned *row = (unsigned *)(keep_alive.data() + o_row), *cnt = (unsigned *)(keep_alive.data() + o_cnt);
+	for (size_t j = 0; j < n; j++) {
+		const size_t f = first[ens[j]], m = first[ens[j] + 1] - f;
+		for (size_t i = 0; i < (blk0[j + 1] - blk0[j]) * 64; i++) src[blk0[j] * 64 + i] = i < m ? (long long)(f + i) : -1;
+		row[j] = ens[j];
+		cnt[j] = (unsigned)m;
+	}
+	if ((rc = scratch(pl, SCR_BTAB, bytes, &v))) return rc;
+	char *tab = (char *)v;
+	HIP_TRY(hipMemcpyAsync(tab, keep_alive.data(), bytes, hipMemcpyHostToDevice, st));
+	const long long *d_src = (const long long *)tab;
+	const unsigned *d_row = (const unsigned *)(tab + o_row), *d_cnt = (const unsigned *)(tab + o_cnt);
+
+	TlPass P;
+	if ((rc = tspws_tl_pass_setup_f32(pl, total, nslots, &P))) return rc;
+	const TlTable &T = *P.T;
+	if ((rc = scratch(pl, SCR_BXG, P.batch * N * sizeof(float), &v))) return rc;
+	float *xg = (float *)v;
+	const size_t R = round_size(pl, n, 0);
+	RoundBufs b;
+	if ((rc = round_bufs(pl, R, &b))) return rc;
+	for (size_t r0 = 0; r0 < n; r0 += R) {
+		const size_t r1 = std::min(n, r0 + R);
+		pl->batch_stats.rounds++;
+		// the round's blocks in batches of the pass (whole blocks: an ensemble may straddle two batches)
+		for (size_t c0 = blk0[r0]; c0 < blk0[r1]; c0 += P.batch / 64) {
+			const size_t c1 = std::min(blk0[r1], c0 + P.batch / 64);
+			const unsigned nb = (unsigned)((c1 - c0) * 64);
+			pl->batch_stats.pass_batches++;
+			hipLaunchKernelGGL(k_batch_gather, dim3((unsigned)((N + 255) / 256), nb), dim3(256), 0, st, d_x, ld, d_src + c0 * 64, (unsigned)N, xg);
+			if ((rc = tspws_tl_pass_transform_f32(pl, &P, xg, N, nb, st))) return rc;
+			// the segments of the ensembles in this batch; runs of consecutive segments with the same geometry share one launch
+			size_t j = std::upper_bound(blk0.begin(), blk0.end(), c0) - blk0.begin() - 1;
+			while (j < r1 && blk0[j] < c1) {
+				struct Seg { size_t b0, nblk, ntr; bool head, tail; unsigned m; };
+				auto seg = [&](size_t e) {
+					Seg s;
+					const size_t m = cnt[e], s0 = std::max(blk0[e], c0), s1 = std::min(blk0[e + 1], c1);
+					s.b0 = s0; s.nblk = s1 - s0;
+					s.ntr = std::min(m, (s1 - blk0[e]) * 64) - (s0 - blk0[e]) * 64;
+					s.head = s0 == blk0[e]; s.tail = s1 == blk0[e + 1]; s.m = (unsigned)m;
+					return s;
+				};
+				const Seg a = seg(j);
+				size_t k = j + 1;
+				while (k < r1 && blk0[k] < c1) {
+					const Seg s = seg(k);
+					if (s.nblk != a.nblk || s.ntr != a.ntr || s.head != a.head || s.tail != a.tail || (a.tail && s.m != a.m)) break;
+					k++;
+				}
+				const size_t jr = j - r0; // stack of the round
+				FuseOut fz;
+				fz.accST = P.planes + (a.b0 - c0) * 2 * nc; fz.accPS = fz.accST + nc; fz.stride = 2 * nc; fz.tps = 64; fz.applied = true;
+				AccExtra ex;
+				ex.y_fz = a.nblk * 2 * nc;
+				WeightArgs wa;
+				wa.OUT = b.Y + 2 * jr * nc; wa.out_stride = 2 * nc;
+				wa.mode = tspws_weight_mode(p->wu, p->unbiased, a.m); wa.K = wa.M = (double)a.m; wa.wu = p->wu;
+				const double2 *part = P.part ? P.part + (a.b0 - c0) * 64 * T.npart : nullptr;
+				tspws_launch_accumulate(pl, part, (unsigned)a.ntr, b.Y + (2 * jr + 1) * nc, b.PS + 2 * jr * nc, a.head ? 1 : 0, &fz, (unsigned)a.nblk, st,
+				                        (unsigned)(k - j), a.nblk * 64 * T.npart, 2 * nc, &T, a.tail ? &wa : nullptr, ScaleRange(), &ex);
+				j = k;
+			}
+		}
+		if ((rc = round_finish(pl, b, (unsigned)(r1 - r0), d_row + r0, d_cnt + r0, d_ls, d_ts, st))) return rc;
+	}
+	return 0;
+}
+
+// Two-stage ensembles `ens` (Kmax <= M_b): one streaming pass for all their partial-stack rows, the rows through the few-trace forward.
+int batch_two_stage(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *first, const std::vector<unsigned> &ens,
+                    size_t total, float *d_ls, float *d_ts, hipStream_t st, HostTables &keep)
+{
+	const size_t N = pl->N, nc = pl->ncoef, n = ens.size();
+	const unsigned K = p->Kmax;
+	int rc;
+	void *v;
+	const size_t o_cnt = n * sizeof(unsigned), o_mv = (o_cnt + n * sizeof(unsigned) + 7) & ~(size_t)7, bytes = o_mv + n * sizeof(double);
+	keep.blob.assign(bytes, 0);
+	unsigned *row = (unsigned *)keep.blob.data(), *cnt = (unsigned *)(keep.blob.data() + o_cnt);
+	double *Mv = (double *)(keep.blob.data() + o_mv);
+	for (size_t j = 0; j < n; j++) {
+		row[j] = ens[j];
+		cnt[j] = (unsigned)(first[ens[j] + 1] - first[ens[j]]);
+		Mv[j] = (double)cnt[j];
+	}
+	if ((rc = scratch(pl, SCR_BTAB, bytes, &v))) return rc;
+	char *tab = (char *)v;
+	HIP_TRY(hipMemcpyAsync(tab, keep.blob.data(), bytes, hipMemcpyHostToDevice, st));
+	const unsigned *d_row = (const unsigned *)tab, *d_cnt = (const unsigned *)(tab + o_cnt);
+	const double *d_Mv = (const double *)(tab + o_mv);
+
+	// every ensemble's streaming work items: group g = floor(i Kmax / M_b) of its traces (ts_pws1f_lib.c:876), cut into equal pieces
+	const unsigned clen = tspws_chunk_len_for(N, total / n);
+	std::vector<Chunk> all;
+	std::vector<size_t> ck0(n + 1, 0); // items of ensemble j: [ck0[j], ck0[j + 1]), in group order (row = g)
+	for (size_t j = 0; j < n; j++) {
+		const size_t f = first[ens[j]], m = cnt[j];
+		size_t i = 0;
+		while (i < m) {
+			const size_t g = (size_t)floor((double)(i * (size_t)K) / (double)m);
+			size_t e = i + 1;
+			while (e < m && (size_t)floor((double)(e * (size_t)K) / (double)m) == g) e++;
+			const size_t cn = e - i, pieces = (cn + clen - 1) / clen, base = cn / pieces, rem = cn % pieces;
+			size_t t = f + i;
+			for (size_t k = 0; k < pieces; k++) {
+				Chunk c; c.t0 = t; c.count = (unsigned)(base + (k < rem ? 1 : 0)); c.row = (unsigned)g;
+				all.push_back(c);
+				t += c.count;
+			}
+			i = e;
+		}
+		ck0[j + 1] = all.size();
+	}
+	// rounds: the per-stack blocks, the rows (SCR_BP) and their partials (SCR_PART) of at most R ensembles, and the chunk sums of the streaming
+	// pass (SCR_CHUNK, N doubles per work item, tspws_chunks_launch) within the budget
+	const size_t R = round_size(pl, n, std::max((size_t)K * pl->npart * sizeof(double2), (size_t)K * N * sizeof(double)));
+	const size_t ck_cap = std::max<size_t>(1, tspws_part_budget_bytes() / (((N + 3) & ~(size_t)3) * sizeof(double)));
+	RoundBufs b;
+	if ((rc = round_bufs(pl, R, &b))) return rc;
+	if ((rc = scratch(pl, SCR_BP, R * K * N * sizeof(double), &v))) return rc;
+	double *rows = (double *)v;
+	if ((rc = scratch(pl, SCR_PART, R * K * pl->npart * sizeof(double2), &v))) return rc;
+	double2 *part = (double2 *)v;
+	for (size_t r0 = 0, r1; r0 < n; r0 = r1) {
+		r1 = r0 + 1;
+		while (r1 < n && r1 - r0 < R && ck0[r1 + 1] - ck0[r0] <= ck_cap) r1++;
+		const size_t nr = r1 - r0;
+		pl->batch_stats.rounds++;
+		// chunk table of the round: row jr * K + g = group g of stack jr
+		keep.chunks.emplace_back(all.begin() + ck0[r0], all.begin() + ck0[r1]);
+		keep.row_first.emplace_back(nr * K + 1, 0);
+		std::vector<Chunk> &ck = keep.chunks.back();
+		std::vector<unsigned> &rf = keep.row_first.back();
+		for (size_t jr = 0; jr < nr; jr++)
+			for (size_t q = ck0[r0 + jr] - ck0[r0]; q < ck0[r0 + jr + 1] - ck0[r0]; q++) ck[q].row += (unsigned)(jr * K);
+		for (size_t q = ck.size(); q-- > 0;) rf[ck[q].row] = (unsigned)q; // (every group has traces: Kmax <= M_b)
+		rf[nr * K] = (unsigned)ck.size();
+		if ((rc = tspws_run_chunks(pl, d_x, ld, N, ck, rf, (unsigned)(nr * K), rows, N, st, false))) return rc;
+		if ((rc = tspws_forward_parts_f64(pl, rows, nr * K, N, part, st, nullptr, ScaleRange()))) return rc;
+		WeightArgs wa;
+		wa.OUT = b.Y; wa.out_stride = 2 * nc;
+		wa.mode = tspws_weight_mode(p->wu, p->unbiased, K); wa.K = (double)K; wa.wu = p->wu; wa.Mv = d_Mv + r0;
+		tspws_launch_accumulate(pl, part, K, b.Y + nc, b.PS, 1, nullptr, 0, st, (unsigned)nr, (size_t)K * pl->npart, 2 * nc, nullptr, &wa, ScaleRange());
+		if ((rc = round_finish(pl, b, (unsigned)nr, d_row + r0, d_cnt + r0, d_ls, d_ts, st))) return rc;
+	}
+	return 0;
+}
+
+} // namespace
+
+extern "C" int tspws_hip_stack_batch(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *h_first, unsigned B,
+                                     float *d_ls, float *d_ts, void *s)
+{
+	if (!pl || !p || !h_first) return fail(TSPWS_E_ARG, "stack_batch: NULL");
+	if (!B) return 0;
+	if (!d_ls || !d_ts) return fail(TSPWS_E_ARG, "stack_batch: NULL output");
+	for (unsigned b = 0; b < B; b++)
+		if (h_first[b + 1] < h_first[b]) return fail(TSPWS_E_ARG, "stack_batch: decreasing ensemble offsets");
+	const size_t N = pl->N;
+	const bool any = h_first[B] > h_first[0];
+	if (any && !d_x) return fail(TSPWS_E_ARG, "stack_batch: NULL traces");
+	if (any && ld < N) return fail(TSPWS_E_ARG, "stack_batch: row stride below the trace length");
+	HIP_TRY(hipSetDevice(pl->device));
+	hipStream_t st = S_(s);
+	int rc;
+	std::vector<unsigned> one, two; // ensembles with traces by stage rule
+	size_t n1 = 0, n2 = 0;
+	for (unsigned b = 0; b < B; b++) {
+		const size_t m = h_first[b + 1] - h_first[b];
+		if (!m) continue;
+		if (is_two_stage(p, m)) { two.push_back(b); n2 += m; }
+		else { one.push_back(b); n1 += m; }
+	}
+	HostTables tab1, tab2;
+	pl->batch_stats = tspws_hip_batch_stats();
+	pl->batch_stats.empty = B - (unsigned)(one.size() + two.size());
+	if (one.size() > 1 && tspws_many_trace_path(pl, n1)) {
+		pl->batch_stats.single_pass = (unsigned)one.size();
+		if ((rc = batch_single(pl, p, d_x, ld, h_first, one, n1, d_ls, d_ts, st, tab1))) return rc;
+	} else {
+		pl->batch_stats.looped += (unsigned)one.size();
+		for (unsigned b : one)
+			if ((rc = tspws_hip_stack(pl, p, d_x + h_first[b] * ld, ld, h_first[b + 1] - h_first[b], d_ls + (size_t)b * N, d_ts + (size_t)b * N, s))) return rc;
+	}
+	if (two.size() > 1) {
+		pl->batch_stats.two_stage_pass = (unsigned)two.size();
+		if ((rc = batch_two_stage(pl, p, d_x, ld, h_first, two, n2, d_ls, d_ts, st, tab2))) return rc;
+	} else {
+		pl->batch_stats.looped += (unsigned)two.size();
+		for (unsigned b : two)
+			if ((rc = tspws_hip_stack(pl, p, d_x + h_first[b] * ld, ld, h_first[b + 1] - h_first[b], d_ls + (size_t)b * N, d_ts + (size_t)b * N, s))) return rc;
+	}
+	// empty ensembles: zero rows
+	for (unsigned b = 0; b < B; b++)
+		if (h_first[b + 1] == h_first[b]) {
+			HIP_TRY(hipMemsetAsync(d_ls + (size_t)b * N, 0, N * sizeof(float), st));
+			HIP_TRY(hipMemsetAsync(d_ts + (size_t)b * N, 0, N * sizeof(float), st));
+		}
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(st)); // outputs complete; the host tables of the uploads go out of scope
+	return 0;
+}
+
+extern "C" int tspws_hip_stack_batch_stats(const tspws_hip_plan *pl, tspws_hip_batch_stats *stats)
+{
+	if (!pl || !stats) return fail(TSPWS_E_ARG, "stack_batch_stats: NULL");
+	*stats = pl->batch_stats;
+	return 0;
+}

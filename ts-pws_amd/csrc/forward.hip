@@ -770,117 +770,148 @@ static unsigned fuse_tps(const tspws_hip_plan *p, size_t nb)
 
 // Many traces (single-stage stacks): trace-lane kernel on the transposed batch (fwd_tl.h); the stacks of the fused scales
 // come back as one plane pair per 64-trace block, the split / coarse scales as per-trace partials in the tl layout.
+// The pass in two pieces that the batched call (batch.hip) shares: the decomposition and scratch of a pass (engine by ntr traces,
+// batches sized for nslots), and the transforms of one batch.
 template <typename TIn>
-static int stacks_tl(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t ld, double *d_ST, double *d_PS, hipStream_t st, bool keep,
-                     const WeightArgs *wa, bool *weighted)
+static int tl_pass_setup(tspws_hip_plan *p, size_t ntr, size_t nslots, TlPass &P)
 {
 	int rc;
 	void *v;
 	// decomposition: many trace blocks and more than two voices per octave -> tl[0], else tl[1] (tspws_build_forward)
-	unsigned pick = ((ntr + 63) / 64 >= 12 && p->V > 2) ? 0u : 1u;
+	unsigned pick = ((nslots + 63) / 64 >= 12 && p->V > 2) ? 0u : 1u;
 	if (const char *e = sweep_env("TSPWS_TL_PICK")) pick = atoi(e) ? 1u : 0u; // sweeps: force a decomposition
 	// ... or the spectral engine for the far-decimated octaves (spectral.hip) with its own decomposition of the rest
 	SpecDecomp *dc = nullptr;
 	const unsigned spec_first = tspws_spectral_choice(p, ntr);
-	if (spec_first < p->S && (rc = tspws_spectral_decomp(p, spec_first, (unsigned)std::min<size_t>((ntr + 63) / 64, 64), &dc))) return rc;
+	if (spec_first < p->S && (rc = tspws_spectral_decomp(p, spec_first, (unsigned)std::min<size_t>((nslots + 63) / 64, 64), &dc))) return rc;
 	const TlTable &T = dc ? dc->T : p->tl[p->tl[pick].n ? pick : 1u - pick]; // (a short frame may leave one of them without trace-lane items)
 	// traces per batch: transposed copy <= 1 GiB, at most 4096 (64 plane pairs), a multiple of 64
 	size_t batch = std::min<size_t>(4096, std::max<size_t>(64, (((size_t)1 << 30) / ((size_t)p->N * sizeof(TIn))) & ~(size_t)63));
 	if (T.npart) batch = std::min(batch, std::max<size_t>(64, (tspws_part_budget_bytes() / (T.npart * sizeof(double2))) & ~(size_t)63));
 	if (const char *e = sweep_env("TSPWS_TL_BATCH")) batch = std::max<size_t>(64, (size_t)atoi(e) & ~(size_t)63); // tests: force several batches
-	batch = std::min(batch, (ntr + 63) & ~(size_t)63);
+	batch = std::min(batch, (nslots + 63) & ~(size_t)63);
 	const size_t nblk_max = batch / 64;
 	if ((rc = scratch(p, SCR_XT, (size_t)p->N * batch * sizeof(TIn), &v))) return rc;
-	TIn *xT = (TIn *)v;
+	P.xT = v;
 	if ((rc = scratch(p, SCR_FZ, nblk_max * 2 * p->ncoef * sizeof(double2), &v))) return rc;
-	double2 *planes = (double2 *)v;
-	double2 *part = nullptr, *gsum = nullptr;
-	if (T.npart) { if ((rc = scratch(p, SCR_PART, batch * T.npart * sizeof(double2), &v))) return rc; part = (double2 *)v; }
-	if (T.gcoltiles) { if ((rc = scratch(p, SCR_GEMM, (size_t)T.gKS * batch * T.gcoltiles * 16 * sizeof(double2), &v))) return rc; gsum = (double2 *)v; }
+	P.planes = (double2 *)v;
+	P.part = P.gsum = nullptr;
+	if (T.npart) { if ((rc = scratch(p, SCR_PART, batch * T.npart * sizeof(double2), &v))) return rc; P.part = (double2 *)v; }
+	if (T.gcoltiles) { if ((rc = scratch(p, SCR_GEMM, (size_t)T.gKS * batch * T.gcoltiles * 16 * sizeof(double2), &v))) return rc; P.gsum = (double2 *)v; }
+	P.dc = dc; P.T = &T; P.batch = batch;
+	return 0;
+}
+
+template <typename TIn>
+static int tl_pass_transform(tspws_hip_plan *p, const TlPass &P, const TIn *xb, size_t ld, unsigned nb, hipStream_t st)
+{
+	int rc;
+	SpecDecomp *dc = P.dc;
+	const TlTable &T = *P.T;
+	const unsigned nblk = (nb + 63) / 64, TP = nblk * 64;
+	TIn *xT = (TIn *)P.xT;
+	double2 *planes = P.planes, *part = P.part, *gsum = P.gsum;
+	// the direct kernel (scales with too few outputs for the trace-lane kernel: latency-bound, tl partial layout) on the side
+	// stream: it reads the traces themselves, so it starts with the transposition and runs beside the trace-lane kernel
+	hipStream_t sp = st;
+	bool poly_join = false;
+	// order of the matrix-pipe kernel for the coarsest scales (fwd_gemm.h): 1 = on the caller's stream BEHIND the trace-lane kernel (default: the
+	// chain is the longer branch, and its transform passes are at their slowest with a second kernel beside them at the start -- 499 x 16501:
+	// 0.631 ms; 500 x 20000: 0.731), 0 = in front of the trace-lane kernel (0.662 / 0.769), 2 = on a third stream beside both (0.644 / 0.777);
+	// TSPWS_GEMM_ORDER, sweeps (tools/experiments/r6_gemm_order.sh)
+	static const int gemm_order = sweep_env("TSPWS_GEMM_ORDER") ? atoi(sweep_env("TSPWS_GEMM_ORDER")) : 1;
+	auto launch_gemm = [&](hipStream_t gs) {
+		hipLaunchKernelGGL((k_fwd_gemm<TIn>), dim3((T.gcoltiles + 3) / 4, T.gKS, nblk), dim3(256), 0, gs, (const TIn *)xT, TP, nb, p->N,
+		                   (const GemmCol *)T.d_gcols, T.gcoltiles, T.gKC, (const double2 *)p->d_w, gsum);
+		const size_t nred = (size_t)nb * T.gcoltiles * 16;
+		hipLaunchKernelGGL(k_gemm_reduce, dim3((unsigned)((nred + 255) / 256)), dim3(256), 0, gs, (const double2 *)gsum, TP, nb, T.gcoltiles * 16, T.gKS,
+		                   (const GemmCol *)T.d_gcols, part, T.npart);
+	};
+	if ((T.waves || (T.gcoltiles && gemm_order == 2)) && dc) {
+		// the direct kernel of a spectral decomposition: the scales whose filters are too long for the transform window (N not a power of two:
+		// the clipped scales of the shipped example's frame, ~9 % of its FIR work) or middle octaves that fit neither the trace-lane kernel nor
+		// the set.  It reads the traces themselves: a third stream, forked here, joined before the accumulation -- beside the chain and
+		// the trace-lane kernel
+		const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
+		if (!p->xs) HIP_TRY(hipStreamCreateWithFlags(&p->xs, hipStreamNonBlocking));
+		if (!p->ev_xs0) HIP_TRY(hipEventCreateWithFlags(&p->ev_xs0, evf));
+		if (!p->ev_xs1) HIP_TRY(hipEventCreateWithFlags(&p->ev_xs1, evf));
+		HIP_TRY(hipEventRecord(p->ev_xs0, st)); // (after the previous batch's accumulation: `part` is free again)
+		HIP_TRY(hipStreamWaitEvent(p->xs, p->ev_xs0, 0));
+		const unsigned nbw = (T.waves + 3) / 4;
+		for (size_t u0 = 0; T.waves && u0 < nb; u0 += 2 * 32768) {
+			const unsigned nt = (unsigned)std::min<size_t>(nb - u0, 2 * 32768);
+			hipLaunchKernelGGL((k_fwd_poly<TIn, 2>), dim3(nbw, (nt + 1) / 2), dim3(256), 0, p->xs, xb + u0 * ld, ld, nt, p->N, T.d_sc, p->S, p->d_w,
+			                   part + u0 * T.npart, T.npart, T.waves);
+		}
+		poly_join = true;
+	} else if (T.waves) {
+		const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
+		if (!p->side) HIP_TRY(tspws_side_stream(p));
+		if (!p->ev_fork) HIP_TRY(hipEventCreateWithFlags(&p->ev_fork, evf));
+		if (!p->ev_join) HIP_TRY(hipEventCreateWithFlags(&p->ev_join, evf));
+		HIP_TRY(hipEventRecord(p->ev_fork, st)); // (after the previous batch's accumulation: `part` is free again)
+		HIP_TRY(hipStreamWaitEvent(p->side, p->ev_fork, 0));
+		sp = p->side;
+		const unsigned nbw = (T.waves + 3) / 4;
+		for (size_t u0 = 0; u0 < nb; u0 += 2 * 32768) {
+			const unsigned nt = (unsigned)std::min<size_t>(nb - u0, 2 * 32768);
+			hipLaunchKernelGGL((k_fwd_poly<TIn, 2>), dim3(nbw, (nt + 1) / 2), dim3(256), 0, sp, xb + u0 * ld, ld, nt, p->N, T.d_sc, p->S, p->d_w,
+			                   part + u0 * T.npart, T.npart, T.waves);
+		}
+	}
+	// (a batch with a spectral set: the transposition also leaves the traces' maxima for the chain)
+	if (dc) { if ((rc = spectral_transpose_t(p, xb, ld, nb, xT, TP, st))) return rc; }
+	else hipLaunchKernelGGL((k_transpose_traces<TIn>), dim3((p->N + 63) / 64, nblk), dim3(256), 0, st, xb, ld, nb, p->N, TP, xT);
+	// the spectral chain (transforms through HBM / MALL: bandwidth-bound) beside the trace-lane kernel (FP64-bound) on the side stream
+	static const bool spec_serial = sweep_env("TSPWS_SPEC_SERIAL") != nullptr; // sweeps: one after the other
+	if (dc && ((T.n && !spec_serial) || (T.gcoltiles && gemm_order == 2))) {
+		const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
+		if (!p->side) HIP_TRY(tspws_side_stream(p));
+		if (!p->ev_fork) HIP_TRY(hipEventCreateWithFlags(&p->ev_fork, evf));
+		if (!p->ev_join) HIP_TRY(hipEventCreateWithFlags(&p->ev_join, evf));
+		HIP_TRY(hipEventRecord(p->ev_fork, st)); // (after the transposition)
+		if (T.n && !spec_serial) { HIP_TRY(hipStreamWaitEvent(p->side, p->ev_fork, 0)); sp = p->side; }
+		if (T.gcoltiles && gemm_order == 2) { HIP_TRY(hipStreamWaitEvent(p->xs, p->ev_fork, 0)); launch_gemm(p->xs); }
+	}
+	if (T.gcoltiles && gemm_order == 0) launch_gemm(st);
+	if (dc && (rc = spectral_run_t(p, dc, (const TIn *)xT, TP, nb, planes, planes + p->ncoef, 2 * p->ncoef, nullptr, dc && T.n && !spec_serial ? sp : st))) return rc;
+	if (T.n)
+		hipLaunchKernelGGL((k_fwd_tl<TIn>), dim3(T.wgs, nblk), dim3(TL_NT), T.lds, st, (const TIn *)xT, TP, nb, p->N, T.d_items, T.n, p->d_w,
+		                   planes, planes + p->ncoef, 2 * p->ncoef, part, T.npart);
+	if (T.gcoltiles && gemm_order == 1) launch_gemm(st);
+	if (sp != st) {
+		HIP_TRY(hipEventRecord(p->ev_join, sp));
+		HIP_TRY(hipStreamWaitEvent(st, p->ev_join, 0));
+	}
+	if (poly_join) {
+		HIP_TRY(hipEventRecord(p->ev_xs1, p->xs));
+		HIP_TRY(hipStreamWaitEvent(st, p->ev_xs1, 0));
+	}
+	return 0;
+}
+
+int tspws_tl_pass_setup_f32(tspws_hip_plan *p, size_t ntr, size_t nslots, TlPass *P) { return tl_pass_setup<float>(p, ntr, nslots, *P); }
+int tspws_tl_pass_transform_f32(tspws_hip_plan *p, const TlPass *P, const float *xb, size_t ld, unsigned nb, hipStream_t st)
+{
+	return tl_pass_transform<float>(p, *P, xb, ld, nb, st);
+}
+
+template <typename TIn>
+static int stacks_tl(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t ld, double *d_ST, double *d_PS, hipStream_t st, bool keep,
+                     const WeightArgs *wa, bool *weighted)
+{
+	int rc;
+	TlPass P;
+	if ((rc = tl_pass_setup<TIn>(p, ntr, ntr, P))) return rc;
+	const size_t batch = P.batch;
 	for (size_t t0 = 0; t0 < ntr; t0 += batch) {
-		const unsigned nb = (unsigned)std::min(batch, ntr - t0), nblk = (nb + 63) / 64, TP = nblk * 64;
-		const TIn *xb = d_x + t0 * ld;
-		// the direct kernel (scales with too few outputs for the trace-lane kernel: latency-bound, tl partial layout) on the side
-		// stream: it reads the traces themselves, so it starts with the transposition and runs beside the trace-lane kernel
-		hipStream_t sp = st;
-		bool poly_join = false;
-		// order of the matrix-pipe kernel for the coarsest scales (fwd_gemm.h): 1 = on the caller's stream BEHIND the trace-lane kernel (default: the
-		// chain is the longer branch, and its transform passes are at their slowest with a second kernel beside them at the start -- 499 x 16501:
-		// 0.631 ms; 500 x 20000: 0.731), 0 = in front of the trace-lane kernel (0.662 / 0.769), 2 = on a third stream beside both (0.644 / 0.777);
-		// TSPWS_GEMM_ORDER, sweeps (tools/experiments/r6_gemm_order.sh)
-		static const int gemm_order = sweep_env("TSPWS_GEMM_ORDER") ? atoi(sweep_env("TSPWS_GEMM_ORDER")) : 1;
-		auto launch_gemm = [&](hipStream_t gs) {
-			hipLaunchKernelGGL((k_fwd_gemm<TIn>), dim3((T.gcoltiles + 3) / 4, T.gKS, nblk), dim3(256), 0, gs, (const TIn *)xT, TP, nb, p->N,
-			                   (const GemmCol *)T.d_gcols, T.gcoltiles, T.gKC, (const double2 *)p->d_w, gsum);
-			const size_t nred = (size_t)nb * T.gcoltiles * 16;
-			hipLaunchKernelGGL(k_gemm_reduce, dim3((unsigned)((nred + 255) / 256)), dim3(256), 0, gs, (const double2 *)gsum, TP, nb, T.gcoltiles * 16, T.gKS,
-			                   (const GemmCol *)T.d_gcols, part, T.npart);
-		};
-		if ((T.waves || (T.gcoltiles && gemm_order == 2)) && dc) {
-			// the direct kernel of a spectral decomposition: the scales whose filters are too long for the transform window (N not a power of two:
-			// the clipped scales of the shipped example's frame, ~9 % of its FIR work) or middle octaves that fit neither the trace-lane kernel nor
-			// the set.  It reads the traces themselves: a third stream, forked here, joined before the accumulation -- beside the chain and
-			// the trace-lane kernel
-			const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
-			if (!p->xs) HIP_TRY(hipStreamCreateWithFlags(&p->xs, hipStreamNonBlocking));
-			if (!p->ev_xs0) HIP_TRY(hipEventCreateWithFlags(&p->ev_xs0, evf));
-			if (!p->ev_xs1) HIP_TRY(hipEventCreateWithFlags(&p->ev_xs1, evf));
-			HIP_TRY(hipEventRecord(p->ev_xs0, st)); // (after the previous batch's accumulation: `part` is free again)
-			HIP_TRY(hipStreamWaitEvent(p->xs, p->ev_xs0, 0));
-			const unsigned nbw = (T.waves + 3) / 4;
-			for (size_t u0 = 0; T.waves && u0 < nb; u0 += 2 * 32768) {
-				const unsigned nt = (unsigned)std::min<size_t>(nb - u0, 2 * 32768);
-				hipLaunchKernelGGL((k_fwd_poly<TIn, 2>), dim3(nbw, (nt + 1) / 2), dim3(256), 0, p->xs, xb + u0 * ld, ld, nt, p->N, T.d_sc, p->S, p->d_w,
-				                   part + u0 * T.npart, T.npart, T.waves);
-			}
-			poly_join = true;
-		} else if (T.waves) {
-			const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
-			if (!p->side) HIP_TRY(tspws_side_stream(p));
-			if (!p->ev_fork) HIP_TRY(hipEventCreateWithFlags(&p->ev_fork, evf));
-			if (!p->ev_join) HIP_TRY(hipEventCreateWithFlags(&p->ev_join, evf));
-			HIP_TRY(hipEventRecord(p->ev_fork, st)); // (after the previous batch's accumulation: `part` is free again)
-			HIP_TRY(hipStreamWaitEvent(p->side, p->ev_fork, 0));
-			sp = p->side;
-			const unsigned nbw = (T.waves + 3) / 4;
-			for (size_t u0 = 0; u0 < nb; u0 += 2 * 32768) {
-				const unsigned nt = (unsigned)std::min<size_t>(nb - u0, 2 * 32768);
-				hipLaunchKernelGGL((k_fwd_poly<TIn, 2>), dim3(nbw, (nt + 1) / 2), dim3(256), 0, sp, xb + u0 * ld, ld, nt, p->N, T.d_sc, p->S, p->d_w,
-				                   part + u0 * T.npart, T.npart, T.waves);
-			}
-		}
-		// (a batch with a spectral set: the transposition also leaves the traces' maxima for the chain)
-		if (dc) { if ((rc = spectral_transpose_t(p, xb, ld, nb, xT, TP, st))) return rc; }
-		else hipLaunchKernelGGL((k_transpose_traces<TIn>), dim3((p->N + 63) / 64, nblk), dim3(256), 0, st, xb, ld, nb, p->N, TP, xT);
-		// the spectral chain (transforms through HBM / MALL: bandwidth-bound) beside the trace-lane kernel (FP64-bound) on the side stream
-		static const bool spec_serial = sweep_env("TSPWS_SPEC_SERIAL") != nullptr; // sweeps: one after the other
-		if (dc && ((T.n && !spec_serial) || (T.gcoltiles && gemm_order == 2))) {
-			const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
-			if (!p->side) HIP_TRY(tspws_side_stream(p));
-			if (!p->ev_fork) HIP_TRY(hipEventCreateWithFlags(&p->ev_fork, evf));
-			if (!p->ev_join) HIP_TRY(hipEventCreateWithFlags(&p->ev_join, evf));
-			HIP_TRY(hipEventRecord(p->ev_fork, st)); // (after the transposition)
-			if (T.n && !spec_serial) { HIP_TRY(hipStreamWaitEvent(p->side, p->ev_fork, 0)); sp = p->side; }
-			if (T.gcoltiles && gemm_order == 2) { HIP_TRY(hipStreamWaitEvent(p->xs, p->ev_fork, 0)); launch_gemm(p->xs); }
-		}
-		if (T.gcoltiles && gemm_order == 0) launch_gemm(st);
-		if (dc && (rc = spectral_run_t(p, dc, (const TIn *)xT, TP, nb, planes, planes + p->ncoef, 2 * p->ncoef, nullptr, dc && T.n && !spec_serial ? sp : st))) return rc;
-		if (T.n)
-			hipLaunchKernelGGL((k_fwd_tl<TIn>), dim3(T.wgs, nblk), dim3(TL_NT), T.lds, st, (const TIn *)xT, TP, nb, p->N, T.d_items, T.n, p->d_w,
-			                   planes, planes + p->ncoef, 2 * p->ncoef, part, T.npart);
-		if (T.gcoltiles && gemm_order == 1) launch_gemm(st);
-		if (sp != st) {
-			HIP_TRY(hipEventRecord(p->ev_join, sp));
-			HIP_TRY(hipStreamWaitEvent(st, p->ev_join, 0));
-		}
-		if (poly_join) {
-			HIP_TRY(hipEventRecord(p->ev_xs1, p->xs));
-			HIP_TRY(hipStreamWaitEvent(st, p->ev_xs1, 0));
-		}
+		const unsigned nb = (unsigned)std::min(batch, ntr - t0), nblk = (nb + 63) / 64;
+		if ((rc = tl_pass_transform<TIn>(p, P, d_x + t0 * ld, ld, nb, st))) return rc;
 		FuseOut fz;
-		fz.accST = planes; fz.accPS = planes + p->ncoef; fz.stride = 2 * p->ncoef; fz.tps = 64; fz.applied = true;
+		fz.accST = P.planes; fz.accPS = P.planes + p->ncoef; fz.stride = 2 * p->ncoef; fz.tps = 64; fz.applied = true;
 		const bool last = t0 + batch >= ntr; // the launch that completes the stacks also weights them (wa)
-		tspws_launch_accumulate(p, part, nb, (double2 *)d_ST, (double2 *)d_PS, (t0 == 0 && !keep) ? 1 : 0, &fz, nblk, st, 1, 0, 0, &T, last && !keep ? wa : nullptr, ScaleRange());
+		tspws_launch_accumulate(p, P.part, nb, (double2 *)d_ST, (double2 *)d_PS, (t0 == 0 && !keep) ? 1 : 0, &fz, nblk, st, 1, 0, 0, P.T, last && !keep ? wa : nullptr, ScaleRange());
 		if (last && !keep && wa && wa->OUT && weighted) *weighted = true;
 	}
 	HIP_TRY(hipGetLastError());

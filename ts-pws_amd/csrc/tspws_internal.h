@@ -9,6 +9,7 @@
 //   stack.hip     the whole call on device-resident traces: local half, finish stage (whole / in pieces / by scales)
 //   resample.hip  jackknife, random subsampling, convergence curves
 //   jk_single.hip single-stage jackknife from per-class stacks
+//   batch.hip     many same-length ensembles in one call
 //   comm.hip      trace shards on several devices of one process: RCCL all-reduce, sharded tspws_main driver
 //
 // Layout in HBM
@@ -171,7 +172,7 @@ struct AccExtra {
 	bool fused_done = false;          // the fused forward kernel completed (and weighted) the stacks of its scales itself: only the others are left
 };
 
-enum { SCR_Y = 0, SCR_PART, SCR_XT, SCR_OBUF, SCR_SEL, SCR_SUBST, SCR_CONV, SCR_CHUNK, SCR_P, SCR_STPS, SCR_OUT, SCR_X2, SCR_CLS, SCR_JKP, SCR_JKOUT, SCR_TAB, SCR_FZ, SCR_JKTAB, SCR_SPA, SCR_SPB, SCR_SPG, SCR_SPH, SCR_SPM, SCR_SPK, SCR_GEMM, SCR_J1TAB, SCR_J1PL, SCR_J1T, SCR_N };
+enum { SCR_Y = 0, SCR_PART, SCR_XT, SCR_OBUF, SCR_SEL, SCR_SUBST, SCR_CONV, SCR_CHUNK, SCR_P, SCR_STPS, SCR_OUT, SCR_X2, SCR_CLS, SCR_JKP, SCR_JKOUT, SCR_TAB, SCR_FZ, SCR_JKTAB, SCR_SPA, SCR_SPB, SCR_SPG, SCR_SPH, SCR_SPM, SCR_SPK, SCR_GEMM, SCR_J1TAB, SCR_J1PL, SCR_J1T, SCR_BTAB, SCR_BXG, SCR_BY, SCR_BX, SCR_BP, SCR_N };
 
 struct OctDesc; // inverse work items (inv_poly.h)
 struct TLItem;  // many-trace forward work items (fwd_tl.h)
@@ -192,6 +193,17 @@ struct TlTable {
 };
 
 struct SpecDecomp; // spectral engine (spectral.h)
+
+// One many-trace pass (forward.hip: stacks_tl and the batched call, batch.hip): the decomposition it takes and its scratch.  A batch of nb
+// traces leaves the stacks of the fused scales as one plane pair per 64-trace block in planes ([blk][ST | PS], 2 ncoef apart) and the other
+// scales as per-trace partials in part (T->npart apart: the layout of T's scale table).
+struct TlPass {
+	SpecDecomp *dc = nullptr;   // spectral set of the pass (nullptr: FIR kernels only)
+	const TlTable *T = nullptr; // decomposition of the rest
+	size_t batch = 0;           // traces per batch, a multiple of 64
+	void *xT = nullptr;         // the batch transposed
+	double2 *planes = nullptr, *part = nullptr, *gsum = nullptr;
+};
 
 struct tspws_hip_plan {
 	int device = 0, type = -1;
@@ -258,6 +270,7 @@ struct tspws_hip_plan {
 	// were outgrown: a caller may still hold the old pointer (e.g. as the buffer of an in-flight collective), so they live
 	// until plan_destroy
 	std::vector<void *> retired;
+	tspws_hip_batch_stats batch_stats{}; // how the last batched call (batch.hip) stacked its ensembles
 };
 
 int tspws_scratch(tspws_hip_plan *p, int slot, size_t bytes, void **out);
@@ -340,6 +353,9 @@ __device__ __forceinline__ double2 weight_value(const double2 st, const double2 
 int  tspws_build_forward(tspws_hip_plan *p);              // work decomposition of the forward kernels (few-trace and many-trace tables)
 int  tspws_forward_parts_f32(tspws_hip_plan *p, const float *d_x, size_t ntr, size_t ld, double2 *d_part, hipStream_t st, FuseOut *fz, ScaleRange rg);
 int  tspws_forward_parts_f64(tspws_hip_plan *p, const double *d_x, size_t ntr, size_t ld, double2 *d_part, hipStream_t st, FuseOut *fz, ScaleRange rg);
+// many-trace pass: engine and decomposition by ntr traces, batches for nslots; then the transforms of one batch of nb traces at xb
+int  tspws_tl_pass_setup_f32(tspws_hip_plan *p, size_t ntr, size_t nslots, TlPass *P);
+int  tspws_tl_pass_transform_f32(tspws_hip_plan *p, const TlPass *P, const float *xb, size_t ld, unsigned nb, hipStream_t st);
 int  tspws_join_fir_stream(tspws_hip_plan *p, hipStream_t fir, hipStream_t st); // FuseOut::defer_fir_join: st waits for what is enqueued on fir
 // ST / PS of ntr traces (keep: add to the stacks already there; wa: weighting applied by the launch that completes the
 // stacks, *weighted tells whether that happened; rg: only these scales)
