@@ -240,11 +240,12 @@ class Plan:
         check(self.lib.tspws_hip_reduce_buffer(self.h, C.byref(self.params), mtr_global, C.byref(ptr), C.byref(n)), "reduce_buffer")
         return _as_tensor(ptr.value, n.value, torch.float64, self.device)
 
-    def _traces(self, traces):
+    def _traces(self, traces, dtype=None):
         """(rows, row stride) of a float32 [mtr][N] device tensor after checking what the C ABI cannot see."""
         import torch
-        if traces.dtype != torch.float32 or traces.dim() != 2 or traces.shape[1] != self.N:
-            raise TspwsError(f"traces must be float32 [mtr][{self.N}], got {traces.dtype} {tuple(traces.shape)}")
+        dtype = dtype or torch.float32
+        if traces.dtype != dtype or traces.dim() != 2 or traces.shape[1] != self.N:
+            raise TspwsError(f"traces must be {dtype} [mtr][{self.N}], got {traces.dtype} {tuple(traces.shape)}")
         if traces.shape[0] and traces.stride(1) != 1:
             raise TspwsError("traces must be contiguous along the samples (stride(1) == 1)")
         if not traces.is_cuda or (traces.device.index or 0) != self.device:
@@ -260,6 +261,25 @@ class Plan:
         if t.dtype != torch.float32 or t.numel() < self.N or not t.is_contiguous() or not t.is_cuda or (t.device.index or 0) != self.device:
             raise TspwsError(f"{name} must be a contiguous float32 tensor of >= {self.N} samples on cuda:{self.device}")
         return t.data_ptr()
+
+    def stacks(self, traces):
+        """The two FP64 planes of the rows of `traces` -- linear stack ST = sum Y_t and phase stack PS = sum Y_t / |Y_t| -- as complex128
+        numpy arrays of ncoef: tspws_hip_stacks_float for float32 [mtr][N] rows, tspws_hip_stacks_double for float64 ones (the partial
+        stacks of a two-stage call).  The device buffers hold NaN before the call (the entry points clear them: an unwritten coefficient
+        shows); synchronises."""
+        import numpy as np
+        import torch
+        if traces.dtype not in (torch.float32, torch.float64):
+            raise TspwsError(f"traces must be float32 or float64 [mtr][{self.N}], got {traces.dtype}")
+        mtr, ld = self._traces(traces, traces.dtype)
+        if not mtr:
+            raise TspwsError("stacks needs at least one row")
+        fn = self.lib.tspws_hip_stacks_float if traces.dtype == torch.float32 else self.lib.tspws_hip_stacks_double
+        ST = torch.full((2 * self.ncoef,), float("nan"), dtype=torch.float64, device=traces.device)
+        PS = torch.full((2 * self.ncoef,), float("nan"), dtype=torch.float64, device=traces.device)
+        check(fn(self.h, traces.data_ptr(), mtr, ld, ST.data_ptr(), PS.data_ptr(), self._stream()), "stacks")
+        torch.cuda.synchronize(traces.device)
+        return ST.cpu().numpy().view(np.complex128), PS.cpu().numpy().view(np.complex128)
 
     def stack_local(self, traces, first=0, mtr_global=None):
         mtr, ld = self._traces(traces)
