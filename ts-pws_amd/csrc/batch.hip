@@ -119,7 +119,7 @@ int batch_single(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t 
 	const unsigned *d_row = (const unsigned *)(tab + o_row), *d_cnt = (const unsigned *)(tab + o_cnt);
 
 	TlPass P;
-	if ((rc = tspws_tl_pass_setup_f32(pl, total, nslots, &P))) return rc;
+	if ((rc = tspws_tl_pass_setup<float>(pl, total, nslots, P))) return rc;
 	const TlTable &T = *P.T;
 	if ((rc = scratch(pl, SCR_BXG, P.batch * N * sizeof(float), &v))) return rc;
 	float *xg = (float *)v;
@@ -135,7 +135,7 @@ int batch_single(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t 
 			const unsigned nb = (unsigned)((c1 - c0) * 64);
 			pl->batch_stats.pass_batches++;
 			hipLaunchKernelGGL(k_batch_gather, dim3((unsigned)((N + 255) / 256), nb), dim3(256), 0, st, d_x, ld, d_src + c0 * 64, (unsigned)N, xg);
-			if ((rc = tspws_tl_pass_transform_f32(pl, &P, xg, N, nb, st))) return rc;
+			if ((rc = tspws_tl_pass_transform<float>(pl, P, xg, N, nb, st))) return rc;
 			// the segments of the ensembles in this batch; runs of consecutive segments with the same geometry share one launch
 			size_t j = std::upper_bound(blk0.begin(), blk0.end(), c0) - blk0.begin() - 1;
 			while (j < r1 && blk0[j] < c1) {
@@ -244,7 +244,7 @@ int batch_two_stage(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size
 		for (size_t q = ck.size(); q-- > 0;) rf[ck[q].row] = (unsigned)q; // (every group has traces: Kmax <= M_b)
 		rf[nr * K] = (unsigned)ck.size();
 		if ((rc = tspws_run_chunks(pl, d_x, ld, N, ck, rf, (unsigned)(nr * K), rows, N, st, false))) return rc;
-		if ((rc = tspws_forward_parts_f64(pl, rows, nr * K, N, part, st, nullptr, ScaleRange()))) return rc;
+		if ((rc = tspws_forward_parts<double>(pl, rows, nr * K, N, part, st, nullptr, ScaleRange()))) return rc;
 		WeightArgs wa;
 		wa.OUT = b.Y; wa.out_stride = 2 * nc;
 		wa.mode = tspws_weight_mode(p->wu, p->unbiased, K); wa.K = (double)K; wa.wu = p->wu; wa.Mv = d_Mv + r0;

@@ -352,22 +352,22 @@ static LaunchRange launch_range(const tspws_hip_plan *p, ScaleRange rg)
 	return r;
 }
 
-// The side stream of the direct kernel.  TSPWS_SIDE_PRIO=1 / -1 creates it with the highest / lowest stream priority (sweeps: does
-// the coarse-scale kernel finish inside the main kernel's time when it is dispatched first?); default: plain.
-static hipError_t tspws_side_stream(tspws_hip_plan *p)
+// The direct kernel for ntr >= 2 traces, two per workgroup row: the waves [wav0, wav1) of the scale table d_sc, at most 2 x 32768 traces per launch
+template <typename TIn>
+static void launch_poly2(const tspws_hip_plan *p, const TIn *d_x, size_t ld, size_t ntr, const ScaleDesc *d_sc, double2 *d_part, size_t npart, unsigned wav1,
+                         unsigned wav0, hipStream_t st)
 {
-	const char *e = sweep_env("TSPWS_SIDE_PRIO");
-	if (!e || !atoi(e)) return hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking);
-	int lo = 0, hi = 0;
-	hipError_t rc = hipDeviceGetStreamPriorityRange(&lo, &hi);
-	if (rc != hipSuccess) return rc;
-	return hipStreamCreateWithPriority(&p->side, hipStreamNonBlocking, atoi(e) > 0 ? hi : lo);
+	for (size_t t0 = 0; t0 < ntr; t0 += 2 * 32768) {
+		const unsigned nt = (unsigned)std::min<size_t>(ntr - t0, 2 * 32768);
+		hipLaunchKernelGGL((k_fwd_poly<TIn, 2>), dim3((wav1 - wav0 + 3) / 4, (nt + 1) / 2), dim3(256), 0, st, d_x + t0 * ld, ld, nt, p->N, d_sc, p->S, p->d_w,
+		                   d_part + t0 * npart, npart, wav1, wav0);
+	}
 }
 
 // Two independent kernels transform disjoint sets of scales: the LDS kernel (FP64-bound) and the direct kernel (coarse
 // scales, latency-bound).  They run side by side: a side stream is forked from and joined back into the caller's stream.
 template <typename TIn>
-static int forward_parts(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t ld, double2 *d_part, hipStream_t st, FuseOut *fz, ScaleRange rg)
+int tspws_forward_parts(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t ld, double2 *d_part, hipStream_t st, FuseOut *fz, ScaleRange rg)
 {
 	if (fz) { fz->applied = false; fz->spec_first = p->S; }
 	bool spec_join = false;
@@ -409,21 +409,13 @@ static int forward_parts(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t l
 						// workgroups free -- but with the streams of a SECOND plan alive in the process any non-default priority costs 0.4-0.5 ms:
 						// 2.00 / 2.46 ms least urgent, 2.10 / 2.56 most urgent, 2.03 / 2.03 plain, 2.10 / 2.10 one after the other;
 						// docs/history/experiments/r5_cfg4_robust.sh, 150 calls each.)  TSPWS_XS_PRIO (sweeps): -1 least, 1 most urgent
-						const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
-						if (!p->xs) {
-							int plo = 0, phi = 0;
-							HIP_TRY(hipDeviceGetStreamPriorityRange(&plo, &phi)); // (plo = least urgent)
-							const char *e = sweep_env("TSPWS_XS_PRIO");
-							HIP_TRY(hipStreamCreateWithPriority(&p->xs, hipStreamNonBlocking, e ? (atoi(e) > 0 ? phi : atoi(e) < 0 ? plo : 0) : 0));
-						}
-						if (!p->ev_xs1) HIP_TRY(hipEventCreateWithFlags(&p->ev_xs1, evf));
-						if (!p->ev_xs2) HIP_TRY(hipEventCreateWithFlags(&p->ev_xs2, evf));
+						if ((rc = tspws_plan_stream(p, p->xs)) || (rc = tspws_plan_event(p->ev_xs2))) return rc;
 						behind_tr = fz->ev_mid ? fz->ev_mid : p->ev_xs2;
 					}
 					if ((rc = tspws_spectral_rows_f64(p, dc, (const double *)d_x, ld, (unsigned)ntr, fz->tps, *fz, st, behind_tr))) return rc;
 					fz->spec_first = sf;
 					if (behind_tr) { // side by side: the FIR kernels (and the caller's readers of the rows: ev_mid) wait for the transposition only
-						HIP_TRY(hipStreamWaitEvent(p->xs, behind_tr, 0));
+						if ((rc = tspws_fork(p, st, p->xs, p->ev_xs2, behind_tr))) return rc; // (the chain recorded it)
 						fz->mid_recorded = behind_tr == fz->ev_mid;
 						fir = p->xs;
 					} else if (fz->ev_mid) { HIP_TRY(hipEventRecord(fz->ev_mid, st)); fz->mid_recorded = true; } // one after the other: behind the whole chain
@@ -443,31 +435,18 @@ static int forward_parts(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t l
 	constexpr bool serial = false;
 #endif
 	if (has_lds && has_poly && !serial) {
-		const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence; // device-local ordering only
-		if (!p->side) HIP_TRY(tspws_side_stream(p));
-		if (!p->ev_fork) HIP_TRY(hipEventCreateWithFlags(&p->ev_fork, evf));
-		if (!p->ev_join) HIP_TRY(hipEventCreateWithFlags(&p->ev_join, evf));
 		// fork: the side stream waits for the producer of d_x -- its launch carried the event (plan->le.ready) or a record here
-		hipEvent_t ready = p->le.ready;
-		if (!ready || fir != st) { ready = p->ev_fork; HIP_TRY(hipEventRecord(ready, fir)); }
-		HIP_TRY(hipStreamWaitEvent(p->side, ready, 0));
+		if (int rc = tspws_fork(p, fir, p->side, p->ev_fork, fir == st ? p->le.ready : nullptr)) return rc;
 		sp = p->side;
 	}
 	p->le.ready = nullptr; // (valid for the first transforms after the producer only)
 	// the direct kernel first: its few hundred long, latency-bound workgroups (no LDS, 116 VGPRs) get their slots and the
 	// LDS kernel's workgroups fill in beside them
 	if (has_poly) {
-		const unsigned nb = (lr.wav1 - lr.wav0 + 3) / 4;
-		if (ntr == 1) {
-			hipLaunchKernelGGL((k_fwd_poly<TIn, 1>), dim3(nb, 1), dim3(256), 0, sp, d_x, ld, 1u, p->N, p->d_sc, p->S, p->d_w, d_part,
+		if (ntr == 1)
+			hipLaunchKernelGGL((k_fwd_poly<TIn, 1>), dim3((lr.wav1 - lr.wav0 + 3) / 4, 1), dim3(256), 0, sp, d_x, ld, 1u, p->N, p->d_sc, p->S, p->d_w, d_part,
 			                   p->npart, lr.wav1, lr.wav0);
-		} else {
-			for (size_t t0 = 0; t0 < ntr; t0 += 2 * 32768) {
-				const unsigned nt = (unsigned)std::min<size_t>(ntr - t0, 2 * 32768);
-				hipLaunchKernelGGL((k_fwd_poly<TIn, 2>), dim3(nb, (nt + 1) / 2), dim3(256), 0, sp, d_x + t0 * ld, ld, nt, p->N, p->d_sc,
-				                   p->S, p->d_w, d_part + t0 * p->npart, p->npart, lr.wav1, lr.wav0);
-			}
-		}
+		else launch_poly2<TIn>(p, d_x, ld, ntr, p->d_sc, d_part, p->npart, lr.wav1, lr.wav0, sp);
 	}
 	if (has_lds) {
 		const bool fuse = fz && fz->accST && p->n_fusable;
@@ -491,36 +470,16 @@ static int forward_parts(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t l
 		}
 		if (fuse) fz->applied = true;
 	}
-	if (sp != fir) {
-		HIP_TRY(hipEventRecord(p->ev_join, sp));
-		HIP_TRY(hipStreamWaitEvent(fir, p->ev_join, 0));
-	}
+	if (sp != fir) if (int rc = tspws_join(sp, fir, p->ev_join)) return rc;
 	if (spec_join) {
-		if (fz && fz->defer_fir_join) fz->fir_stream = p->xs; // (the caller enqueues more behind the FIR kernels and joins: tspws_join_fir_stream)
-		else {
-			HIP_TRY(hipEventRecord(p->ev_xs1, p->xs));
-			HIP_TRY(hipStreamWaitEvent(st, p->ev_xs1, 0));
-		}
+		if (fz && fz->defer_fir_join) fz->fir_stream = p->xs; // (the caller enqueues more behind the FIR kernels and joins them itself, through ev_xs1)
+		else if (int rc = tspws_join(p->xs, st, p->ev_xs1)) return rc;
 	}
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
-
-int tspws_join_fir_stream(tspws_hip_plan *p, hipStream_t fir, hipStream_t st)
-{
-	HIP_TRY(hipEventRecord(p->ev_xs1, fir));
-	HIP_TRY(hipStreamWaitEvent(st, p->ev_xs1, 0));
-	return 0;
-}
-
-int tspws_forward_parts_f32(tspws_hip_plan *p, const float *d_x, size_t ntr, size_t ld, double2 *d_part, hipStream_t st, FuseOut *fz, ScaleRange rg)
-{
-	return forward_parts<float>(p, d_x, ntr, ld, d_part, st, fz, rg);
-}
-int tspws_forward_parts_f64(tspws_hip_plan *p, const double *d_x, size_t ntr, size_t ld, double2 *d_part, hipStream_t st, FuseOut *fz, ScaleRange rg)
-{
-	return forward_parts<double>(p, d_x, ntr, ld, d_part, st, fz, rg);
-}
+template int tspws_forward_parts<float>(tspws_hip_plan *, const float *, size_t, size_t, double2 *, hipStream_t, FuseOut *, ScaleRange);
+template int tspws_forward_parts<double>(tspws_hip_plan *, const double *, size_t, size_t, double2 *, hipStream_t, FuseOut *, ScaleRange);
 
 #if FL_ABLATE
 // debug build only: only the log2(D) classes of k_fwd_lds named by the hex mask TSPWS_FWD_CLASSES run (results wrong: timing ablation)
@@ -602,13 +561,6 @@ unsigned tspws_spectral_choice(const tspws_hip_plan *p, size_t ntr)
 	return tspws_spectral_first_scale(p, nsmax_env ? nsmax_env : std::max(512u, (p->N + dmin - 1) / dmin));
 }
 
-static int spectral_transpose_t(tspws_hip_plan *p, const float *d_x, size_t ld, unsigned ntr, float *xT, unsigned TP, hipStream_t st) { return tspws_spectral_transpose_f32(p, d_x, ld, ntr, xT, TP, st); }
-static int spectral_transpose_t(tspws_hip_plan *p, const double *d_x, size_t ld, unsigned ntr, double *xT, unsigned TP, hipStream_t st) { return tspws_spectral_transpose_f64(p, d_x, ld, ntr, xT, TP, st); }
-static int spectral_run_t(tspws_hip_plan *p, SpecDecomp *dc, const float *xT, unsigned TP, unsigned ntr, double2 *ST, double2 *PS, size_t stride, double2 *Y, hipStream_t st)
-{ return tspws_spectral_run_f32(p, dc, xT, TP, ntr, ST, PS, stride, Y, st); }
-static int spectral_run_t(tspws_hip_plan *p, SpecDecomp *dc, const double *xT, unsigned TP, unsigned ntr, double2 *ST, double2 *PS, size_t stride, double2 *Y, hipStream_t st)
-{ return tspws_spectral_run_f64(p, dc, xT, TP, ntr, ST, PS, stride, Y, st); }
-
 bool tspws_many_trace_path(const tspws_hip_plan *p, size_t ntr)
 {
 	if (tspws_generic_forward()) return false;
@@ -632,7 +584,7 @@ static int forward_impl(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t ld
 	if (rc) return rc;
 	for (size_t t0 = 0; t0 < ntr; t0 += batch) {
 		const size_t nb = std::min(batch, ntr - t0);
-		if ((rc = forward_parts<TIn>(p, d_x + t0 * ld, nb, ld, (double2 *)v, st, nullptr, ScaleRange()))) return rc;
+		if ((rc = tspws_forward_parts<TIn>(p, d_x + t0 * ld, nb, ld, (double2 *)v, st, nullptr, ScaleRange()))) return rc;
 		hipLaunchKernelGGL(k_gather_parts, dim3((unsigned)((p->ncoef + 255) / 256), (unsigned)nb), dim3(256), 0, st, (const double2 *)v,
 		                   p->npart, p->d_sc, p->S, (double2 *)d_Y + t0 * p->ncoef, p->ncoef);
 	}
@@ -668,8 +620,8 @@ static int forward_spectral(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_
 	TIn *xT = (TIn *)v;
 	for (size_t t0 = 0; t0 < ntr; t0 += batch) {
 		const unsigned nb = (unsigned)std::min(batch, ntr - t0), nblk = (nb + 63) / 64, TP = nblk * 64;
-		if ((rc = spectral_transpose_t(p, d_x + t0 * ld, ld, nb, xT, TP, st))) return rc;
-		if ((rc = spectral_run_t(p, dc, (const TIn *)xT, TP, nb, nullptr, nullptr, 0, (double2 *)d_Y + t0 * p->ncoef, st))) return rc;
+		if ((rc = tspws_spectral_transpose<TIn>(p, d_x + t0 * ld, ld, nb, xT, TP, st))) return rc;
+		if ((rc = tspws_spectral_run<TIn>(p, dc, (const TIn *)xT, TP, nb, nullptr, nullptr, 0, (double2 *)d_Y + t0 * p->ncoef, st))) return rc;
 	}
 	HIP_TRY(hipGetLastError());
 	return 0;
@@ -773,7 +725,7 @@ static unsigned fuse_tps(const tspws_hip_plan *p, size_t nb)
 // The pass in two pieces that the batched call (batch.hip) shares: the decomposition and scratch of a pass (engine by ntr traces,
 // batches sized for nslots), and the transforms of one batch.
 template <typename TIn>
-static int tl_pass_setup(tspws_hip_plan *p, size_t ntr, size_t nslots, TlPass &P)
+int tspws_tl_pass_setup(tspws_hip_plan *p, size_t ntr, size_t nslots, TlPass &P)
 {
 	int rc;
 	void *v;
@@ -803,7 +755,7 @@ static int tl_pass_setup(tspws_hip_plan *p, size_t ntr, size_t nslots, TlPass &P
 }
 
 template <typename TIn>
-static int tl_pass_transform(tspws_hip_plan *p, const TlPass &P, const TIn *xb, size_t ld, unsigned nb, hipStream_t st)
+int tspws_tl_pass_transform(tspws_hip_plan *p, const TlPass &P, const TIn *xb, size_t ld, unsigned nb, hipStream_t st)
 {
 	int rc;
 	SpecDecomp *dc = P.dc;
@@ -832,70 +784,37 @@ static int tl_pass_transform(tspws_hip_plan *p, const TlPass &P, const TIn *xb, 
 		// the clipped scales of the shipped example's frame, ~9 % of its FIR work) or middle octaves that fit neither the trace-lane kernel nor
 		// the set.  It reads the traces themselves: a third stream, forked here, joined before the accumulation -- beside the chain and
 		// the trace-lane kernel
-		const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
-		if (!p->xs) HIP_TRY(hipStreamCreateWithFlags(&p->xs, hipStreamNonBlocking));
-		if (!p->ev_xs0) HIP_TRY(hipEventCreateWithFlags(&p->ev_xs0, evf));
-		if (!p->ev_xs1) HIP_TRY(hipEventCreateWithFlags(&p->ev_xs1, evf));
-		HIP_TRY(hipEventRecord(p->ev_xs0, st)); // (after the previous batch's accumulation: `part` is free again)
-		HIP_TRY(hipStreamWaitEvent(p->xs, p->ev_xs0, 0));
-		const unsigned nbw = (T.waves + 3) / 4;
-		for (size_t u0 = 0; T.waves && u0 < nb; u0 += 2 * 32768) {
-			const unsigned nt = (unsigned)std::min<size_t>(nb - u0, 2 * 32768);
-			hipLaunchKernelGGL((k_fwd_poly<TIn, 2>), dim3(nbw, (nt + 1) / 2), dim3(256), 0, p->xs, xb + u0 * ld, ld, nt, p->N, T.d_sc, p->S, p->d_w,
-			                   part + u0 * T.npart, T.npart, T.waves);
-		}
+		if ((rc = tspws_fork(p, st, p->xs, p->ev_xs0))) return rc; // (after the previous batch's accumulation: `part` is free again)
+		if (T.waves) launch_poly2<TIn>(p, xb, ld, nb, T.d_sc, part, T.npart, T.waves, 0u, p->xs);
 		poly_join = true;
 	} else if (T.waves) {
-		const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
-		if (!p->side) HIP_TRY(tspws_side_stream(p));
-		if (!p->ev_fork) HIP_TRY(hipEventCreateWithFlags(&p->ev_fork, evf));
-		if (!p->ev_join) HIP_TRY(hipEventCreateWithFlags(&p->ev_join, evf));
-		HIP_TRY(hipEventRecord(p->ev_fork, st)); // (after the previous batch's accumulation: `part` is free again)
-		HIP_TRY(hipStreamWaitEvent(p->side, p->ev_fork, 0));
+		if ((rc = tspws_fork(p, st, p->side, p->ev_fork))) return rc; // (after the previous batch's accumulation: `part` is free again)
 		sp = p->side;
-		const unsigned nbw = (T.waves + 3) / 4;
-		for (size_t u0 = 0; u0 < nb; u0 += 2 * 32768) {
-			const unsigned nt = (unsigned)std::min<size_t>(nb - u0, 2 * 32768);
-			hipLaunchKernelGGL((k_fwd_poly<TIn, 2>), dim3(nbw, (nt + 1) / 2), dim3(256), 0, sp, xb + u0 * ld, ld, nt, p->N, T.d_sc, p->S, p->d_w,
-			                   part + u0 * T.npart, T.npart, T.waves);
-		}
+		launch_poly2<TIn>(p, xb, ld, nb, T.d_sc, part, T.npart, T.waves, 0u, sp);
 	}
 	// (a batch with a spectral set: the transposition also leaves the traces' maxima for the chain)
-	if (dc) { if ((rc = spectral_transpose_t(p, xb, ld, nb, xT, TP, st))) return rc; }
+	if (dc) { if ((rc = tspws_spectral_transpose<TIn>(p, xb, ld, nb, xT, TP, st))) return rc; }
 	else hipLaunchKernelGGL((k_transpose_traces<TIn>), dim3((p->N + 63) / 64, nblk), dim3(256), 0, st, xb, ld, nb, p->N, TP, xT);
 	// the spectral chain (transforms through HBM / MALL: bandwidth-bound) beside the trace-lane kernel (FP64-bound) on the side stream
 	static const bool spec_serial = sweep_env("TSPWS_SPEC_SERIAL") != nullptr; // sweeps: one after the other
 	if (dc && ((T.n && !spec_serial) || (T.gcoltiles && gemm_order == 2))) {
-		const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
-		if (!p->side) HIP_TRY(tspws_side_stream(p));
-		if (!p->ev_fork) HIP_TRY(hipEventCreateWithFlags(&p->ev_fork, evf));
-		if (!p->ev_join) HIP_TRY(hipEventCreateWithFlags(&p->ev_join, evf));
-		HIP_TRY(hipEventRecord(p->ev_fork, st)); // (after the transposition)
-		if (T.n && !spec_serial) { HIP_TRY(hipStreamWaitEvent(p->side, p->ev_fork, 0)); sp = p->side; }
-		if (T.gcoltiles && gemm_order == 2) { HIP_TRY(hipStreamWaitEvent(p->xs, p->ev_fork, 0)); launch_gemm(p->xs); }
+		// one record (after the transposition) for both streams
+		hipEvent_t forked = nullptr;
+		if (T.n && !spec_serial) { if ((rc = tspws_fork(p, st, p->side, p->ev_fork))) return rc; sp = p->side; forked = p->ev_fork; }
+		if (T.gcoltiles && gemm_order == 2) { if ((rc = tspws_fork(p, st, p->xs, p->ev_fork, forked))) return rc; launch_gemm(p->xs); }
 	}
 	if (T.gcoltiles && gemm_order == 0) launch_gemm(st);
-	if (dc && (rc = spectral_run_t(p, dc, (const TIn *)xT, TP, nb, planes, planes + p->ncoef, 2 * p->ncoef, nullptr, dc && T.n && !spec_serial ? sp : st))) return rc;
+	if (dc && (rc = tspws_spectral_run<TIn>(p, dc, (const TIn *)xT, TP, nb, planes, planes + p->ncoef, 2 * p->ncoef, nullptr, dc && T.n && !spec_serial ? sp : st))) return rc;
 	if (T.n)
 		hipLaunchKernelGGL((k_fwd_tl<TIn>), dim3(T.wgs, nblk), dim3(TL_NT), T.lds, st, (const TIn *)xT, TP, nb, p->N, T.d_items, T.n, p->d_w,
 		                   planes, planes + p->ncoef, 2 * p->ncoef, part, T.npart);
 	if (T.gcoltiles && gemm_order == 1) launch_gemm(st);
-	if (sp != st) {
-		HIP_TRY(hipEventRecord(p->ev_join, sp));
-		HIP_TRY(hipStreamWaitEvent(st, p->ev_join, 0));
-	}
-	if (poly_join) {
-		HIP_TRY(hipEventRecord(p->ev_xs1, p->xs));
-		HIP_TRY(hipStreamWaitEvent(st, p->ev_xs1, 0));
-	}
+	if (sp != st && (rc = tspws_join(sp, st, p->ev_join))) return rc;
+	if (poly_join && (rc = tspws_join(p->xs, st, p->ev_xs1))) return rc;
 	return 0;
 }
-
-int tspws_tl_pass_setup_f32(tspws_hip_plan *p, size_t ntr, size_t nslots, TlPass *P) { return tl_pass_setup<float>(p, ntr, nslots, *P); }
-int tspws_tl_pass_transform_f32(tspws_hip_plan *p, const TlPass *P, const float *xb, size_t ld, unsigned nb, hipStream_t st)
-{
-	return tl_pass_transform<float>(p, *P, xb, ld, nb, st);
-}
+template int tspws_tl_pass_setup<float>(tspws_hip_plan *, size_t, size_t, TlPass &); // (batch.hip)
+template int tspws_tl_pass_transform<float>(tspws_hip_plan *, const TlPass &, const float *, size_t, unsigned, hipStream_t);
 
 template <typename TIn>
 static int stacks_tl(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t ld, double *d_ST, double *d_PS, hipStream_t st, bool keep,
@@ -903,11 +822,11 @@ static int stacks_tl(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t ld, d
 {
 	int rc;
 	TlPass P;
-	if ((rc = tl_pass_setup<TIn>(p, ntr, ntr, P))) return rc;
+	if ((rc = tspws_tl_pass_setup<TIn>(p, ntr, ntr, P))) return rc;
 	const size_t batch = P.batch;
 	for (size_t t0 = 0; t0 < ntr; t0 += batch) {
 		const unsigned nb = (unsigned)std::min(batch, ntr - t0), nblk = (nb + 63) / 64;
-		if ((rc = tl_pass_transform<TIn>(p, P, d_x + t0 * ld, ld, nb, st))) return rc;
+		if ((rc = tspws_tl_pass_transform<TIn>(p, P, d_x + t0 * ld, ld, nb, st))) return rc;
 		FuseOut fz;
 		fz.accST = P.planes; fz.accPS = P.planes + p->ncoef; fz.stride = 2 * p->ncoef; fz.tps = 64; fz.applied = true;
 		const bool last = t0 + batch >= ntr; // the launch that completes the stacks also weights them (wa)
@@ -920,7 +839,7 @@ static int stacks_tl(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t ld, d
 
 
 template <typename TIn>
-static int stacks_impl(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t ld, double *d_ST, double *d_PS, hipStream_t st, bool keep,
+int tspws_stacks(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t ld, double *d_ST, double *d_PS, hipStream_t st, bool keep,
                        const WeightArgs *wa, bool *weighted, ScaleRange rg)
 { // keep: add to the stacks already in d_ST / d_PS instead of starting from zero
   // wa: weighting to apply where the stacks are completed (same kernel launch); *weighted tells whether that happened
@@ -965,7 +884,7 @@ static int stacks_impl(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t ld,
 			else { fz.accST = (double2 *)vz; fz.accPS = (double2 *)vz + p->ncoef; fz.stride = 2 * p->ncoef; }
 		}
 		const bool all = nb == ntr && !keep; // one batch holds every trace: the accumulation completes the stacks
-		if ((rc = forward_parts<TIn>(p, d_x + t0 * ld, nb, ld, (double2 *)v, st, fuse ? &fz : nullptr, rg))) return rc;
+		if ((rc = tspws_forward_parts<TIn>(p, d_x + t0 * ld, nb, ld, (double2 *)v, st, fuse ? &fz : nullptr, rg))) return rc;
 		tspws_launch_accumulate(p, (const double2 *)v, (unsigned)nb, (double2 *)d_ST, (double2 *)d_PS, zero_first, &fz, nsl, st, 1, 0, 0, nullptr, all ? wa : nullptr, rg);
 		if (all && wa && wa->OUT && weighted) *weighted = true;
 	}
@@ -973,25 +892,17 @@ static int stacks_impl(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t ld,
 	return 0;
 }
 
-int tspws_stacks_f32(tspws_hip_plan *p, const float *d_x, size_t ntr, size_t ld, double *d_ST, double *d_PS, hipStream_t st, bool keep,
-                     const WeightArgs *wa, bool *weighted, ScaleRange rg)
-{
-	return stacks_impl<float>(p, d_x, ntr, ld, d_ST, d_PS, st, keep, wa, weighted, rg);
-}
-int tspws_stacks_f64(tspws_hip_plan *p, const double *d_x, size_t ntr, size_t ld, double *d_ST, double *d_PS, hipStream_t st, bool keep,
-                     const WeightArgs *wa, bool *weighted, ScaleRange rg)
-{
-	return stacks_impl<double>(p, d_x, ntr, ld, d_ST, d_PS, st, keep, wa, weighted, rg);
-}
+template int tspws_stacks<float>(tspws_hip_plan *, const float *, size_t, size_t, double *, double *, hipStream_t, bool, const WeightArgs *, bool *, ScaleRange);
+template int tspws_stacks<double>(tspws_hip_plan *, const double *, size_t, size_t, double *, double *, hipStream_t, bool, const WeightArgs *, bool *, ScaleRange);
 
 extern "C" int tspws_hip_stacks_double(tspws_hip_plan *p, const double *d_P, unsigned K, size_t ldP, double *d_ST, double *d_PS, void *s)
 {
 	if (!p || !d_P || !d_ST || !d_PS) return fail(TSPWS_E_ARG, "stacks_double: NULL");
-	return stacks_impl<double>(p, d_P, K, ldP, d_ST, d_PS, S_(s), false, nullptr, nullptr, ScaleRange());
+	return tspws_stacks<double>(p, d_P, K, ldP, d_ST, d_PS, S_(s), false, nullptr, nullptr, ScaleRange());
 }
 
 extern "C" int tspws_hip_stacks_float(tspws_hip_plan *p, const float *d_x, size_t mtr, size_t ld, double *d_ST, double *d_PS, void *s)
 {
 	if (!p || !d_x || !d_ST || !d_PS) return fail(TSPWS_E_ARG, "stacks_float: NULL");
-	return stacks_impl<float>(p, d_x, mtr, ld, d_ST, d_PS, S_(s), false, nullptr, nullptr, ScaleRange());
+	return tspws_stacks<float>(p, d_x, mtr, ld, d_ST, d_PS, S_(s), false, nullptr, nullptr, ScaleRange());
 }

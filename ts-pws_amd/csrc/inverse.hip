@@ -219,6 +219,37 @@ bool tspws_generic_inverse()
 	return v == 1;
 }
 
+// The waves [w0, w1) of the polyphase inverse's launch list for nb NREC-set reconstructions (grid.y) on `st`, into the octave buffer (*obuf: inv_nslots
+// rows per set): the LDS-staged instantiation below the LDS bound, the per-lane one up to inv_waves_fast, the GEN one above.
+static unsigned inv_nslots(const tspws_hip_plan *p) { return p->inv_noct + (p->inv_ngeneric ? 1 : 0); }
+template <int NREC>
+static int inv_launch_waves(tspws_hip_plan *p, const double2 *Y, unsigned nb, unsigned w0, unsigned w1, hipStream_t st, double **obuf)
+{
+	const size_t slot = (size_t)NREC * p->N, y_coef = (size_t)NREC * p->ncoef, y_obuf = (size_t)inv_nslots(p) * slot;
+	void *v;
+	if (int rc = scratch(p, SCR_OBUF, (size_t)nb * y_obuf * sizeof(double), &v)) return rc;
+	double *ob = *obuf = (double *)v;
+	// the LDS-staged octaves (D = 1: two 80-KB workgroups per CU) run BESIDE the others (latency-bound, eight waves per SIMD) on the
+	// plan's side stream: one after the other they took 64 + 153 us for cfg4's twelve reconstructions, the single per-lane launch 262
+	// (batched reconstructions only: a single pair is 206 vs 197 us that way -- the fork / join and two waves per SIMD cost more than
+	// the one octave's coalescing gains)
+	const unsigned lds_w = nb >= 2 ? p->inv_waves_lds : 0u;
+	const unsigned wl = std::min(std::max(lds_w, w0), w1), wf = std::min(std::max(p->inv_waves_fast, wl), w1); // LDS-staged [w0, wl), per-lane [wl, wf), GEN [wf, w1)
+	const bool beside = wl > w0 && wf > wl;
+	if (beside) if (int rc = tspws_fork(p, st, p->side, p->ev_fork)) return rc;
+	if (wl > w0)
+		hipLaunchKernelGGL((k_inv_poly<NREC, false, true>), dim3((wl - w0 + 3) / 4, nb), dim3(256), 0, beside ? p->side : st, Y, p->ncoef, p->N, p->d_sc, p->d_oc,
+		                   p->inv_noct, p->d_wd, ob, slot, wl, y_coef, y_obuf, w0);
+	if (wf > wl)
+		hipLaunchKernelGGL((k_inv_poly<NREC, false>), dim3((wf - wl + 3) / 4, nb), dim3(256), 0, st, Y, p->ncoef, p->N, p->d_sc, p->d_oc, p->inv_noct, p->d_wd, ob,
+		                   slot, wf, y_coef, y_obuf, wl);
+	if (w1 > wf)
+		hipLaunchKernelGGL((k_inv_poly<NREC, true>), dim3((w1 - wf + 3) / 4, nb), dim3(256), 0, st, Y, p->ncoef, p->N, p->d_sc, p->d_oc, p->inv_noct, p->d_wd, ob,
+		                   slot, w1, y_coef, y_obuf, wf);
+	if (beside) return tspws_join(p->side, st, p->ev_join);
+	return 0;
+}
+
 // nb independent NREC-set reconstructions in one launch (grid.y): set j reads Y + j NREC ncoef, writes x + j NREC N
 // f_ts / f_ls (NREC == 2, nb == 1 only): the stack's float outputs are written by the combining kernel itself (no FP64
 // reconstructions in memory, no epilogue launch); x may then be NULL.
@@ -233,41 +264,12 @@ static int inverse_launch(tspws_hip_plan *p, const double2 *Y, double *x, hipStr
 		                   (size_t)NREC * p->ncoef, slot);
 		return 0;
 	}
-	const unsigned nslots = p->inv_noct + (p->inv_ngeneric ? 1 : 0);
-	void *v;
-	int rc = scratch(p, SCR_OBUF, (size_t)nb * nslots * slot * sizeof(double), &v);
-	if (rc) return rc;
-	double *obuf = (double *)v;
-	// the LDS-staged octaves (D = 1: two 80-KB workgroups per CU) run BESIDE the others (latency-bound, eight waves per SIMD) on the
-	// plan's side stream: one after the other they took 64 + 153 us for cfg4's twelve reconstructions, the single per-lane launch 262
-	// (batched reconstructions only: a single pair is 206 vs 197 us that way -- the fork / join and two waves per SIMD cost more than
-	// the one octave's coalescing gains)
-	const unsigned lds_w = nb >= 2 ? p->inv_waves_lds : 0u;
-	hipStream_t sl = st;
-	const bool beside = lds_w && p->inv_waves_fast > lds_w;
-	if (beside) {
-		const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
-		if (!p->side) HIP_TRY(hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking));
-		if (!p->ev_fork) HIP_TRY(hipEventCreateWithFlags(&p->ev_fork, evf));
-		if (!p->ev_join) HIP_TRY(hipEventCreateWithFlags(&p->ev_join, evf));
-		HIP_TRY(hipEventRecord(p->ev_fork, st));
-		HIP_TRY(hipStreamWaitEvent(p->side, p->ev_fork, 0));
-		sl = p->side;
-	}
-	if (lds_w)
-		hipLaunchKernelGGL((k_inv_poly<NREC, false, true>), dim3((lds_w + 3) / 4, nb), dim3(256), 0, sl, Y, p->ncoef, p->N, p->d_sc, p->d_oc, p->inv_noct,
-		                   p->d_wd, obuf, slot, lds_w, (size_t)NREC * p->ncoef, (size_t)nslots * slot, 0u);
-	if (beside) HIP_TRY(hipEventRecord(p->ev_join, sl));
-	if (p->inv_waves_fast > lds_w)
-		hipLaunchKernelGGL((k_inv_poly<NREC, false>), dim3((p->inv_waves_fast - lds_w + 3) / 4, nb), dim3(256), 0, st, Y, p->ncoef, p->N, p->d_sc, p->d_oc, p->inv_noct,
-		                   p->d_wd, obuf, slot, p->inv_waves_fast, (size_t)NREC * p->ncoef, (size_t)nslots * slot, lds_w);
-	if (p->inv_waves > p->inv_waves_fast)
-		hipLaunchKernelGGL((k_inv_poly<NREC, true>), dim3((p->inv_waves - p->inv_waves_fast + 3) / 4, nb), dim3(256), 0, st, Y, p->ncoef, p->N, p->d_sc,
-		                   p->d_oc, p->inv_noct, p->d_wd, obuf, slot, p->inv_waves, (size_t)NREC * p->ncoef, (size_t)nslots * slot, p->inv_waves_fast);
+	const unsigned nslots = inv_nslots(p);
+	double *obuf;
+	if (int rc = inv_launch_waves<NREC>(p, Y, nb, 0, p->inv_waves, st, &obuf)) return rc;
 	if (p->inv_ngeneric)
 		hipLaunchKernelGGL(k_inverse_generic<NREC>, dim3(nbx, nb), dim3(256), 0, st, Y, p->ncoef, p->N, p->d_sc, p->S, p->d_wd,
 		                   obuf + (size_t)p->inv_noct * slot, 1, (size_t)NREC * p->ncoef, (size_t)nslots * slot);
-	if (beside) HIP_TRY(hipStreamWaitEvent(st, p->ev_join, 0));
 	if (NREC == 2 && nb == 1 && (f_ts || f_ls))
 		if (hipEvent_t e1 = p->le.call_end) { // the call's end event rides on its last launch (tspws_hip_stack)
 			p->le.call_end = nullptr;
@@ -319,34 +321,9 @@ int tspws_inverse_pairs_early(tspws_hip_plan *p, const double2 *Y, unsigned nb, 
 {
 	*done = false;
 	unsigned w_split = 0;
+	double *obuf;
 	if (nb < 2 || !inv_split_point(p, s_split, &w_split)) return 0;
-	const size_t slot = (size_t)2 * p->N;
-	const unsigned nslots = p->inv_noct;
-	void *v;
-	int rc = scratch(p, SCR_OBUF, (size_t)nb * nslots * slot * sizeof(double), &v);
-	if (rc) return rc;
-	double *obuf = (double *)v;
-	const unsigned lds_w = p->inv_waves_lds;
-	if (lds_w && w_split > lds_w) { // the LDS-staged octaves (D = 1) beside the per-lane ones, as in inverse_launch
-		const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
-		if (!p->side) HIP_TRY(hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking));
-		if (!p->ev_fork) HIP_TRY(hipEventCreateWithFlags(&p->ev_fork, evf));
-		if (!p->ev_join) HIP_TRY(hipEventCreateWithFlags(&p->ev_join, evf));
-		HIP_TRY(hipEventRecord(p->ev_fork, early));
-		HIP_TRY(hipStreamWaitEvent(p->side, p->ev_fork, 0));
-		hipLaunchKernelGGL((k_inv_poly<2, false, true>), dim3((lds_w + 3) / 4, nb), dim3(256), 0, p->side, Y, p->ncoef, p->N, p->d_sc, p->d_oc, p->inv_noct,
-		                   p->d_wd, obuf, slot, lds_w, (size_t)2 * p->ncoef, (size_t)nslots * slot, 0u);
-		HIP_TRY(hipEventRecord(p->ev_join, p->side));
-		hipLaunchKernelGGL((k_inv_poly<2, false>), dim3((w_split - lds_w + 3) / 4, nb), dim3(256), 0, early, Y, p->ncoef, p->N, p->d_sc, p->d_oc, p->inv_noct,
-		                   p->d_wd, obuf, slot, w_split, (size_t)2 * p->ncoef, (size_t)nslots * slot, lds_w);
-		HIP_TRY(hipStreamWaitEvent(early, p->ev_join, 0));
-	} else if (lds_w) {
-		hipLaunchKernelGGL((k_inv_poly<2, false, true>), dim3((lds_w + 3) / 4, nb), dim3(256), 0, early, Y, p->ncoef, p->N, p->d_sc, p->d_oc, p->inv_noct,
-		                   p->d_wd, obuf, slot, lds_w, (size_t)2 * p->ncoef, (size_t)nslots * slot, 0u);
-	} else {
-		hipLaunchKernelGGL((k_inv_poly<2, false>), dim3((w_split + 3) / 4, nb), dim3(256), 0, early, Y, p->ncoef, p->N, p->d_sc, p->d_oc, p->inv_noct,
-		                   p->d_wd, obuf, slot, w_split, (size_t)2 * p->ncoef, (size_t)nslots * slot, 0u);
-	}
+	if (int rc = inv_launch_waves<2>(p, Y, nb, 0, w_split, early, &obuf)) return rc; // (the LDS-staged octaves beside the per-lane ones, as in inverse_launch)
 	HIP_TRY(hipGetLastError());
 	*done = true;
 	return 0;
@@ -357,14 +334,9 @@ int tspws_inverse_pairs_late(tspws_hip_plan *p, const double2 *Y, double *x, uns
 	unsigned w_split = 0;
 	if (nb < 2 || !inv_split_point(p, s_split, &w_split)) return fail(TSPWS_E_ARG, "inverse_pairs_late: no early half was launched");
 	const size_t slot = (size_t)2 * p->N;
-	const unsigned nslots = p->inv_noct;
-	void *v;
-	int rc = scratch(p, SCR_OBUF, (size_t)nb * nslots * slot * sizeof(double), &v);
-	if (rc) return rc;
-	double *obuf = (double *)v;
-	hipLaunchKernelGGL((k_inv_poly<2, false>), dim3((p->inv_waves_fast - w_split + 3) / 4, nb), dim3(256), 0, st, Y, p->ncoef, p->N, p->d_sc, p->d_oc, p->inv_noct,
-	                   p->d_wd, obuf, slot, p->inv_waves_fast, (size_t)2 * p->ncoef, (size_t)nslots * slot, w_split);
-	hipLaunchKernelGGL(k_inv_combine, dim3((unsigned)((slot + 255) / 256), nb), dim3(256), 0, st, obuf, slot, nslots, slot, x, (size_t)nslots * slot, slot);
+	double *obuf;
+	if (int rc = inv_launch_waves<2>(p, Y, nb, w_split, p->inv_waves_fast, st, &obuf)) return rc;
+	hipLaunchKernelGGL(k_inv_combine, dim3((unsigned)((slot + 255) / 256), nb), dim3(256), 0, st, obuf, slot, p->inv_noct, slot, x, (size_t)p->inv_noct * slot, slot);
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
@@ -375,10 +347,7 @@ int tspws_inverse_scales(tspws_hip_plan *p, const double2 *Y, double *x2, hipStr
 {
 	const unsigned s_lo = rg.s0, s_hi = rg.s1;
 	const size_t slot = 2 * (size_t)p->N;
-	void *v;
-	int rc = scratch(p, SCR_OBUF, (size_t)p->inv_noct * slot * sizeof(double), &v);
-	if (rc) return rc;
-	double *obuf = (double *)v;
+	double *obuf = nullptr;
 	// the octave items are stored class by class (decimation divides N first), in scale order inside a class: the items
 	// of a scale range are one contiguous run per class
 	unsigned first[2] = {~0u, ~0u}, last[2] = {0, 0};
@@ -390,13 +359,7 @@ int tspws_inverse_scales(tspws_hip_plan *p, const double2 *Y, double *x2, hipStr
 	}
 	for (unsigned c = 0; c < 2; c++) {
 		if (first[c] == ~0u) continue;
-		const unsigned w0 = p->oc_wave_off[first[c]], w1 = p->oc_wave_off[last[c]] + p->oc_nwaves[last[c]];
-		if (c == 0)
-			hipLaunchKernelGGL((k_inv_poly<2, false>), dim3((w1 - w0 + 3) / 4, 1), dim3(256), 0, st, Y, p->ncoef, p->N, p->d_sc, p->d_oc, p->inv_noct, p->d_wd,
-			                   obuf, slot, w1, (size_t)2 * p->ncoef, (size_t)p->inv_noct * slot, w0);
-		else
-			hipLaunchKernelGGL((k_inv_poly<2, true>), dim3((w1 - w0 + 3) / 4, 1), dim3(256), 0, st, Y, p->ncoef, p->N, p->d_sc, p->d_oc, p->inv_noct, p->d_wd,
-			                   obuf, slot, w1, (size_t)2 * p->ncoef, (size_t)p->inv_noct * slot, w0);
+		if (int rc = inv_launch_waves<2>(p, Y, 1, p->oc_wave_off[first[c]], p->oc_wave_off[last[c]] + p->oc_nwaves[last[c]], st, &obuf)) return rc;
 	}
 	const unsigned a0 = first[0] == ~0u ? 0u : first[0], na = first[0] == ~0u ? 0u : last[0] - first[0] + 1;
 	const unsigned b0 = first[1] == ~0u ? 0u : first[1], nb = first[1] == ~0u ? 0u : last[1] - first[1] + 1;

@@ -5,7 +5,7 @@
 // This unit fills that gap with the single-stage resampling body (tspws_subsmpl_float, :501-610) applied to every replica's mask, K
 // replaced by the replica's trace count K_c.  The linear and phase stacks are plain sums over traces, and a delete-d replica is a union
 // of day-of-year bins, so every replica is a sum of per-CLASS stacks (a class = the traces whose selection columns are identical):
-//   class pass   every trace is transformed ONCE (tspws_forward_parts_f32) and added to the ST / PS plane pair of its class
+//   class pass   every trace is transformed ONCE (tspws_forward_parts) and added to the ST / PS plane pair of its class
 //                (k_j1_accumulate, the traces of a class in trace order); the FP64 time-domain class sums feed the linear stacks
 //                (k_j1_time).  The FP64-bound work does not grow with the replica count C.
 //   finish       per batch of replicas: ST_c / PS_c as sums of the kept classes' planes and the weighted coefficients with each
@@ -243,7 +243,7 @@ extern "C" int tspws_hip_jackknife_single(tspws_hip_plan *pl, const t_tsPWS *p, 
 		double2 *part = (double2 *)v;
 		for (size_t b = 0; b < nbat; b++) {
 			const size_t t0 = b * FB, nf = std::min(FB, mtr - t0);
-			if ((rc = tspws_forward_parts_f32(pl, d_x + t0 * ld, nf, ld, part, st, nullptr, ScaleRange()))) return rc;
+			if ((rc = tspws_forward_parts<float>(pl, d_x + t0 * ld, nf, ld, part, st, nullptr, ScaleRange()))) return rc;
 			hipLaunchKernelGGL(k_j1_accumulate, dim3(pl->acc_blocks, ncls), dim3(256), 0, st, (const double2 *)part, pl->npart, (const ScaleDesc *)pl->d_sc, pl->S,
 			                   nc, d_rg + b * ncls, d_idx, t0, planes);
 		}

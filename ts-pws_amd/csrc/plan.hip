@@ -36,6 +36,50 @@ int tspws_scratch(tspws_hip_plan *p, int slot, size_t bytes, void **out)
 	return 0;
 }
 
+// The plan's side streams, created on first use (a plan that never forks creates none) and only here, so that a stream's priority does not
+// depend on which call of the process needed it first.  Plain priority, unless a sweeps build is told otherwise: TSPWS_SIDE_PRIO (p->side: does
+// the coarse-scale kernel finish inside the main kernel's time when it is dispatched first?), TSPWS_XS_PRIO (p->xs) and TSPWS_JK_XFPRIO (p->xf)
+// = 1 / -1 ask for the most / least urgent one (TSPWS_JK_XFPRIO=0 counts as least urgent).  What a wrong priority costs: forward.hip, the
+// few-row spectral chain (0.4-0.5 ms per cfg4 call with a second plan alive).
+int tspws_plan_stream(tspws_hip_plan *p, hipStream_t &s)
+{
+	if (s) return 0;
+	const char *e = sweep_env(&s == &p->side ? "TSPWS_SIDE_PRIO" : &s == &p->xs ? "TSPWS_XS_PRIO" : "TSPWS_JK_XFPRIO");
+	const int v = e ? atoi(e) : 0;
+	if (!v && !(e && &s == &p->xf)) { HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); return 0; }
+	int lo = 0, hi = 0;
+	HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi)); // (lo = least urgent)
+	HIP_TRY(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, v > 0 ? hi : lo));
+	return 0;
+}
+
+// ... and its ordering events: no timing, and device scope -- a system-scope release would write the fresh partial stacks back out of L2
+// (8 us per call).  system_scope: the event behind an upload from the host (the chunk table, stream.hip)
+int tspws_plan_event(hipEvent_t &e, bool system_scope)
+{
+	if (!e) HIP_TRY(hipEventCreateWithFlags(&e, system_scope ? hipEventDisableTiming : hipEventDisableTiming | hipEventDisableSystemFence));
+	return 0;
+}
+
+int tspws_fork(tspws_hip_plan *p, hipStream_t from, hipStream_t &side, hipEvent_t &ev, hipEvent_t carried)
+{
+	if (int rc = tspws_plan_stream(p, side)) return rc;
+	if (!carried) {
+		if (int rc = tspws_plan_event(ev)) return rc;
+		HIP_TRY(hipEventRecord(carried = ev, from));
+	}
+	HIP_TRY(hipStreamWaitEvent(side, carried, 0));
+	return 0;
+}
+
+int tspws_join(hipStream_t side, hipStream_t into, hipEvent_t &ev)
+{
+	if (int rc = tspws_plan_event(ev)) return rc;
+	HIP_TRY(hipEventRecord(ev, side));
+	HIP_TRY(hipStreamWaitEvent(into, ev, 0));
+	return 0;
+}
+
 // ------------------------------------------------------------------------------------------
 // host-side parameter resolution (ts_pws1f_lib.c:91-124)
 // ------------------------------------------------------------------------------------------
@@ -221,19 +265,10 @@ extern "C" void tspws_hip_plan_destroy(tspws_hip_plan *p)
 	(void)hipSetDevice(p->device);
 	for (int i = 0; i < SCR_N; i++) if (p->scr[i]) (void)hipFree(p->scr[i]);
 	for (void *b : p->retired) (void)hipFree(b);
-	if (p->ck_ev) (void)hipEventDestroy(p->ck_ev);
 	for (hipEvent_t e : p->prof_ev) (void)hipEventDestroy(e);
-	if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
-	if (p->ev_join) (void)hipEventDestroy(p->ev_join);
-	if (p->side) (void)hipStreamDestroy(p->side);
-	if (p->xs) (void)hipStreamDestroy(p->xs);
-	if (p->ev_xs0) (void)hipEventDestroy(p->ev_xs0);
-	if (p->ev_xs1) (void)hipEventDestroy(p->ev_xs1);
-	if (p->ev_xs2) (void)hipEventDestroy(p->ev_xs2);
-	if (p->ev_mid) (void)hipEventDestroy(p->ev_mid);
-	if (p->ev_lin) (void)hipEventDestroy(p->ev_lin);
-	if (p->xf) (void)hipStreamDestroy(p->xf);
 	for (hipEvent_t e : p->stage_ev) (void)hipEventDestroy(e);
+	for (hipEvent_t e : {p->ck_ev, p->ev_fork, p->ev_join, p->ev_xs0, p->ev_xs1, p->ev_xs2, p->ev_mid, p->ev_lin}) if (e) (void)hipEventDestroy(e);
+	for (hipStream_t st : {p->side, p->xs, p->xf}) if (st) (void)hipStreamDestroy(st);
 	if (p->d_oc) (void)hipFree(p->d_oc);
 	tspws_spectral_destroy(p);
 	for (TlTable &T : p->tl) { if (T.d_sc) (void)hipFree(T.d_sc); if (T.d_items) (void)hipFree(T.d_items); }

@@ -111,7 +111,7 @@ static int finish_replicas(tspws_hip_plan *pl, const t_tsPWS *p, double *d_P, co
 		// one slice of the fused forward kernel = the KM partial stacks of one replica: its stacks land in the replica's planes
 		FuseOut fz;
 		fz.accST = (double2 *)STr; fz.accPS = (double2 *)STr + nc; fz.stride = 2 * nc; fz.tps = KM;
-		if ((rc = tspws_forward_parts_f64(pl, d_P + (size_t)c0 * KM * N, (size_t)nr * KM, N, part, st, fuse ? &fz : nullptr, ScaleRange()))) return rc;
+		if ((rc = tspws_forward_parts<double>(pl, d_P + (size_t)c0 * KM * N, (size_t)nr * KM, N, part, st, fuse ? &fz : nullptr, ScaleRange()))) return rc;
 		for (unsigned j = 0; j < nr; j++) h_mtr_out[c0 + j] = (unsigned)Kc[c0 + j];
 		// the replicas of the batch side by side in every launch (grid.y): stacks of the scales the fused kernel left out,
 		// weights with each replica's trace count, time-domain linear stacks, inverses two replicas per tap read, outputs
@@ -629,15 +629,10 @@ static int masked_two_stage_pipelined(tspws_hip_plan *pl, const t_tsPWS *p, cons
 	if ((rc = masked_tables(pl, mp, st, dv))) return rc;
 	double *d_Mv = (double *)(dv.tb + mp.o_mv);
 	const unsigned *d_map = (const unsigned *)(dv.tb + mp.o_map);
-	if (!pl->xf) {
-		int lo = 0, hi = 0;
-		HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi)); // (lo = least urgent)
-		const char *e = sweep_env("TSPWS_JK_XFPRIO");
-		HIP_TRY(hipStreamCreateWithPriority(&pl->xf, hipStreamNonBlocking, e ? (atoi(e) > 0 ? hi : lo) : 0));
-	}
+	if ((rc = tspws_plan_stream(pl, pl->xf))) return rc;
 	while (pl->stage_ev.size() < mp.nstage + 1) {
-		hipEvent_t e;
-		HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence));
+		hipEvent_t e = nullptr;
+		if ((rc = tspws_plan_event(e))) return rc;
 		pl->stage_ev.push_back(e);
 	}
 	const unsigned nbx = (unsigned)((N + 255) / 256);
@@ -673,7 +668,7 @@ static int masked_two_stage_pipelined(tspws_hip_plan *pl, const t_tsPWS *p, cons
 			fz.allow_spec = true; // (the far-decimated octaves of these ng W rows may go through the spectral engine: forward.hip decides)
 		}
 		if (fuse && C && sg + 1 == mp.nstage) { // (the linear stacks of the replicas may start behind the spectral chain's transposition, beside the transforms)
-			if (!pl->ev_mid) HIP_TRY(hipEventCreateWithFlags(&pl->ev_mid, hipEventDisableTiming | hipEventDisableSystemFence));
+			if ((rc = tspws_plan_event(pl->ev_mid))) return rc;
 			fz.ev_mid = pl->ev_mid;
 		}
 		// The inverses in two halves (one stage, in-kernel completion, pairs of reconstructions): the octaves of the scales the FIR kernels complete
@@ -684,14 +679,14 @@ static int masked_two_stage_pipelined(tspws_hip_plan *pl, const t_tsPWS *p, cons
 		const bool want_early = fuse && fz.fin.OUT && mp.nstage == 1 && !(nrec & 1u) && !early_off;
 		fz.defer_fir_join = want_early;
 		pl->le.ready = pl->stage_ev[sg]; // the producer's own event: the forward launch's other streams wait for it directly, not for a re-record on xf
-		rc = tspws_forward_parts_f64(pl, d_rows + (size_t)r0 * N, r1 - r0, N, part + (size_t)r0 * pl->npart, fs, fuse ? &fz : nullptr, ScaleRange());
+		rc = tspws_forward_parts<double>(pl, d_rows + (size_t)r0 * N, r1 - r0, N, part + (size_t)r0 * pl->npart, fs, fuse ? &fz : nullptr, ScaleRange());
 		pl->le.ready = nullptr;
 		if (rc) return rc;
 		if (fz.fir_stream) { // the FIR kernels are still un-joined on their stream
 			// (every scale below the chain's must be complete behind the FIR kernels: fused and completed in the kernel -- no pass of k_accumulate_parts)
 			if (fz.spec_first < pl->S && tspws_first_unfused_scale(pl) >= fz.spec_first)
 				if ((rc = tspws_inverse_pairs_early(pl, (const double2 *)OUT, nrec / 2, fz.spec_first, fz.fir_stream, &early_inv))) return rc;
-			if ((rc = tspws_join_fir_stream(pl, fz.fir_stream, fs))) return rc;
+			if ((rc = tspws_join(fz.fir_stream, fs, pl->ev_xs1))) return rc;
 			early_split = fz.spec_first;
 		}
 		if (fuse) stage_spec_first = fz.spec_first;
@@ -708,7 +703,7 @@ static int masked_two_stage_pipelined(tspws_hip_plan *pl, const t_tsPWS *p, cons
 	else if (C && (lin_mid || lin_first)) { // beside the transforms on the second stream: behind the chain's transposition, or (no chain) behind the walk
 		HIP_TRY(hipStreamWaitEvent(pl->xf, lin_mid ? pl->ev_mid : pl->stage_ev[mp.nstage - 1], 0));
 		hipLaunchKernelGGL(k_jk_linear, dim3(nbx, C), dim3(256), 0, pl->xf, (const double *)d_rows, KM, N, (const double *)d_Mv, d_ls_out, W, mp.gps);
-		if (!pl->ev_lin) HIP_TRY(hipEventCreateWithFlags(&pl->ev_lin, hipEventDisableTiming | hipEventDisableSystemFence));
+		if ((rc = tspws_plan_event(pl->ev_lin))) return rc;
 		HIP_TRY(hipEventRecord(pl->ev_lin, pl->xf));
 		lin_side = true;
 	}
@@ -990,7 +985,7 @@ extern "C" int tspws_hip_subsample_sel(tspws_hip_plan *pl, const t_tsPWS *p, con
 	double2 *part = (double2 *)v;
 	for (size_t t0 = 0; t0 < mtr; t0 += FB) {
 		const size_t nf = std::min(FB, mtr - t0);
-		if ((rc = tspws_forward_parts_f32(pl, d_x + t0 * ld, nf, ld, part, st, nullptr, ScaleRange()))) return rc;
+		if ((rc = tspws_forward_parts<float>(pl, d_x + t0 * ld, nf, ld, part, st, nullptr, ScaleRange()))) return rc;
 		hipLaunchKernelGGL(k_accumulate_masked, dim3(pl->acc_blocks, (M + 7) / 8), dim3(256), 0, st, (const double2 *)part, pl->npart, pl->d_sc, pl->S,
 		                   nc, (unsigned)nf, d_sel, mtr, t0, M, STm, PSm);
 	}
@@ -1103,7 +1098,7 @@ extern "C" int tspws_hip_convergence(tspws_hip_plan *pl, const t_tsPWS *p, const
 	if (p->Kmax) { if ((rc = scratch(pl, SCR_P, (size_t)p->Kmax * N * sizeof(double), &v))) return rc; P = (double *)v; }
 	for (size_t i0 = 0; i0 < n_single; i0 += FB) {
 		const unsigned nb = (unsigned)std::min(FB, n_single - i0);
-		if ((rc = tspws_forward_parts_f32(pl, d_x + i0 * ld, nb, ld, part, st, nullptr, ScaleRange()))) return rc;
+		if ((rc = tspws_forward_parts<float>(pl, d_x + i0 * ld, nb, ld, part, st, nullptr, ScaleRange()))) return rc;
 		WeightArgs wa;
 		wa.OUTP = (double2 *)OUTb; wa.outp_stride = nc; wa.k0 = (unsigned)i0; wa.wu = p->wu;
 		wa.mode = tspws_weight_mode(p->wu, p->unbiased, 2); wa.mode1 = tspws_weight_mode(p->wu, p->unbiased, 1);

@@ -1178,8 +1178,8 @@ int tspws_spectral_decomp(tspws_hip_plan *p, unsigned s_first, unsigned nblk_hin
 // Everything between the transposed batch and the planes of the spectral scales.  xT: [N][TP] (TP = nblk 64, pad lanes zero);
 // planes of block tb at ST / PS + tb * stride; Y != NULL: per-trace coefficients [ntr][ncoef] of the spectral scales instead.
 template <typename TIn>
-static int spectral_run(tspws_hip_plan *p, SpecDecomp *dc, const TIn *xT, unsigned TP, unsigned ntr, double2 *ST, double2 *PS, size_t stride, double2 *Y, hipStream_t st,
-                        const SpecRowsOut *ro = nullptr, unsigned tps = 0, unsigned ncol = 0)
+int tspws_spectral_run(tspws_hip_plan *p, SpecDecomp *dc, const TIn *xT, unsigned TP, unsigned ntr, double2 *ST, double2 *PS, size_t stride, double2 *Y, hipStream_t st,
+                       const SpecRowsOut *ro, unsigned tps, unsigned ncol)
 {
 	SpecPlan *sp = dc->sp;
 	const unsigned N = sp->N, M = sp->M, nblk = TP / 64; // (N: the transform length; the traces have sp->Nx samples)
@@ -1199,7 +1199,7 @@ static int spectral_run(tspws_hip_plan *p, SpecDecomp *dc, const TIn *xT, unsign
 		if ((rc = scratch(p, SCR_SPK, (size_t)nblk * sp->nrowcoef * sizeof(unsigned long long), &v))) return rc;
 		mask = (unsigned long long *)v;
 	}
-	// (amax: the largest |sample| of every trace / row, left there by the transposition -- tspws_spectral_transpose_*, spectral_rows)
+	// (amax: the largest |sample| of every trace / row, left there by the transposition -- tspws_spectral_transpose, spectral_rows)
 	// trace transform
 	const size_t np = sp->fwd_bits.size();
 	{
@@ -1345,10 +1345,10 @@ __global__ void __launch_bounds__(1024) k_spec_rowmax(const unsigned long long *
 }
 
 // xT[n][t] = x[t][n] for a batch of ntr traces / rows (TP = padded count, pad lanes zero) + the largest |sample| of each into the plan's
-// SCR_SPM block, where spectral_run looks for them (the noise floor of the transforms scales with it).  One pass over the batch: a pass of its
+// SCR_SPM block, where tspws_spectral_run looks for them (the noise floor of the transforms scales with it).  One pass over the batch: a pass of its
 // own over the transposed copy for the maxima was 26 us at the head of the chain of a 499 x 16501 call.
 template <typename TIn>
-static int spectral_transpose(tspws_hip_plan *p, const TIn *d_x, size_t ld, unsigned ntr, TIn *xT, unsigned TP, hipStream_t st)
+int tspws_spectral_transpose(tspws_hip_plan *p, const TIn *d_x, size_t ld, unsigned ntr, TIn *xT, unsigned TP, hipStream_t st)
 {
 	const unsigned nblk = TP / 64;
 	void *v;
@@ -1360,10 +1360,8 @@ static int spectral_transpose(tspws_hip_plan *p, const TIn *d_x, size_t ld, unsi
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
-int tspws_spectral_transpose_f32(tspws_hip_plan *p, const float *d_x, size_t ld, unsigned ntr, float *xT, unsigned TP, hipStream_t st)
-{ return spectral_transpose<float>(p, d_x, ld, ntr, xT, TP, st); }
-int tspws_spectral_transpose_f64(tspws_hip_plan *p, const double *d_x, size_t ld, unsigned ntr, double *xT, unsigned TP, hipStream_t st)
-{ return spectral_transpose<double>(p, d_x, ld, ntr, xT, TP, st); }
+template int tspws_spectral_transpose<float>(tspws_hip_plan *, const float *, size_t, unsigned, float *, unsigned, hipStream_t);
+template int tspws_spectral_transpose<double>(tspws_hip_plan *, const double *, size_t, unsigned, double *, unsigned, hipStream_t);
 
 template <typename TIn>
 static int spectral_rows(tspws_hip_plan *p, SpecDecomp *dc, const TIn *d_x, size_t ld, unsigned ntr, unsigned tps, const SpecRowsOut &ro, hipStream_t st,
@@ -1374,9 +1372,9 @@ static int spectral_rows(tspws_hip_plan *p, SpecDecomp *dc, const TIn *d_x, size
 	int rc;
 	if ((rc = scratch(p, SCR_XT, (size_t)p->N * TP * sizeof(TIn), &v))) return rc;
 	TIn *xT = (TIn *)v;
-	if ((rc = spectral_transpose<TIn>(p, d_x, ld, ntr, xT, TP, st))) return rc;
+	if ((rc = tspws_spectral_transpose<TIn>(p, d_x, ld, ntr, xT, TP, st))) return rc;
 	if (after_transposition) HIP_TRY(hipEventRecord(after_transposition, st)); // (the rows themselves are not read again by this chain)
-	return spectral_run<TIn>(p, dc, (const TIn *)xT, TP, ntr, nullptr, nullptr, 0, nullptr, st, &ro, tps, ncol);
+	return tspws_spectral_run<TIn>(p, dc, (const TIn *)xT, TP, ntr, nullptr, nullptr, 0, nullptr, st, &ro, tps, ncol);
 }
 
 int tspws_spectral_rows_f64(tspws_hip_plan *p, SpecDecomp *dc, const double *d_x, size_t ld, unsigned ntr, unsigned tps, const FuseOut &fz, hipStream_t st,
@@ -1390,11 +1388,5 @@ int tspws_spectral_rows_f64(tspws_hip_plan *p, SpecDecomp *dc, const double *d_x
 	return spectral_rows<double>(p, dc, d_x, ld, ntr, tps, ro, st, after_transposition);
 }
 
-int tspws_spectral_run_f32(tspws_hip_plan *p, SpecDecomp *dc, const float *xT, unsigned TP, unsigned ntr, double2 *ST, double2 *PS, size_t stride, double2 *Y, hipStream_t st)
-{
-	return spectral_run<float>(p, dc, xT, TP, ntr, ST, PS, stride, Y, st);
-}
-int tspws_spectral_run_f64(tspws_hip_plan *p, SpecDecomp *dc, const double *xT, unsigned TP, unsigned ntr, double2 *ST, double2 *PS, size_t stride, double2 *Y, hipStream_t st)
-{
-	return spectral_run<double>(p, dc, xT, TP, ntr, ST, PS, stride, Y, st);
-}
+template int tspws_spectral_run<float>(tspws_hip_plan *, SpecDecomp *, const float *, unsigned, unsigned, double2 *, double2 *, size_t, double2 *, hipStream_t, const SpecRowsOut *, unsigned, unsigned);
+template int tspws_spectral_run<double>(tspws_hip_plan *, SpecDecomp *, const double *, unsigned, unsigned, double2 *, double2 *, size_t, double2 *, hipStream_t, const SpecRowsOut *, unsigned, unsigned);

@@ -64,7 +64,7 @@ extern "C" int tspws_hip_stack_finish_range(tspws_hip_plan *pl, const t_tsPWS *p
 	int rc;
 	if ((rc = finish_block(pl, &OUT, &ST, &PS))) return rc;
 	if ((rc = tspws_hip_reduce_buffer(pl, p, mtr_global, &P, &nd))) return rc;
-	return tspws_stacks_f64(pl, P + (size_t)g_begin * pl->N, g_end - g_begin, pl->N, ST, PS, S_(s), g_begin != 0, nullptr, nullptr, ScaleRange());
+	return tspws_stacks<double>(pl, P + (size_t)g_begin * pl->N, g_end - g_begin, pl->N, ST, PS, S_(s), g_begin != 0, nullptr, nullptr, ScaleRange());
 }
 
 // weight (unless the accumulation already wrote OUT), both inverse transforms, epilogue (ts_pws1f_lib.c:226-241)
@@ -98,7 +98,7 @@ extern "C" int tspws_hip_stack_finish(tspws_hip_plan *pl, const t_tsPWS *p, size
 		// all Kmax partial stacks at once: the launch that completes ST / PS also writes the weighted coefficients
 		const WeightArgs wa = weight_args(p, OUT, p->Kmax, mtr_global);
 		bool weighted = false;
-		if ((rc = tspws_stacks_f64(pl, B, p->Kmax, pl->N, ST, PS, S_(s), false, &wa, &weighted, ScaleRange()))) return rc;
+		if ((rc = tspws_stacks<double>(pl, B, p->Kmax, pl->N, ST, PS, S_(s), false, &wa, &weighted, ScaleRange()))) return rc;
 		return finish_tail(pl, p, mtr_global, d_ls, d_ts, s, weighted);
 	}
 	HIP_TRY(hipMemcpyAsync(ST, B, 4 * pl->ncoef * sizeof(double), hipMemcpyDeviceToDevice, S_(s)));
@@ -176,7 +176,7 @@ extern "C" int tspws_hip_stack_finish_scales(tspws_hip_plan *pl, const t_tsPWS *
 	const WeightArgs wa = weight_args(p, OUT, p->Kmax, mtr_global);
 	bool weighted = false;
 	ScaleRange rg; rg.s0 = s_begin; rg.s1 = s_end; // the finish-stage launches below cover these scales only
-	if ((rc = tspws_stacks_f64(pl, P, p->Kmax, pl->N, ST, PS, st, false, &wa, &weighted, rg))) return rc;
+	if ((rc = tspws_stacks<double>(pl, P, p->Kmax, pl->N, ST, PS, st, false, &wa, &weighted, rg))) return rc;
 	// (several forward batches: weight afterwards -- over all coefficients; those of other scales are never read)
 	if (!weighted && (rc = tspws_hip_weight(pl, OUT, ST, PS, p->Kmax, (unsigned)mtr_global, p->wu, p->unbiased, s))) return rc;
 	return tspws_inverse_scales(pl, (const double2 *)OUT, d_x2, st, rg);
@@ -252,38 +252,27 @@ extern "C" int tspws_hip_stack(tspws_hip_plan *pl, const t_tsPWS *p, const float
 	// Whatever a path does not consume (single-stage calls, chunked passes, generic kernels) is recorded the ordinary way.
 	const bool prof = pl->prof_used + 3 <= pl->prof_ev.size();
 	hipEvent_t *pe = prof ? &pl->prof_ev[pl->prof_used] : nullptr;
-	if (!pl->ev_fork) HIP_TRY(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming | hipEventDisableSystemFence));
+	if ((rc = tspws_plan_event(pl->ev_fork))) return rc;
 	pl->le = tspws_hip_plan::LaunchEvents();
 	const bool ride = is_two_stage(p, mtr); // the streaming pass of a two-stage call takes both of its events (tspws_run_chunks)
 	if (ride) { pl->le.first_start = prof ? pe[0] : nullptr; pl->le.last_stop = prof ? pe[1] : pl->ev_fork; }
 	else if (prof) HIP_TRY(hipEventRecord(pe[0], S_(s)));
-	if (!ride) {
+	bool weighted = false;
+	if (ride) rc = tspws_hip_stack_local(pl, p, d_x, ld, mtr, 0, mtr, s);
+	else {
 		// single-stage on one device: the launch that completes ST / PS also writes the weighted coefficients -- no copy of the stacks
 		// into the finish block, no weighting pass (the halves stack_local / stack_finish keep them for the all-reduce in between)
 		double *OUT, *ST, *PS;
-		bool weighted = false;
 		if (!(rc = finish_block(pl, &OUT, &ST, &PS))) {
 			const WeightArgs wa = weight_args(p, OUT, (unsigned)mtr, mtr);
-			rc = tspws_stacks_f32(pl, d_x, mtr, ld, ST, PS, S_(s), false, &wa, &weighted, ScaleRange());
+			rc = tspws_stacks<float>(pl, d_x, mtr, ld, ST, PS, S_(s), false, &wa, &weighted, ScaleRange());
 		}
-		if (!rc && prof) rc = hip_rc(hipEventRecord(pe[1], S_(s)), "stack: event");
-		pl->le.call_end = (!rc && prof) ? pe[2] : nullptr;
-		if (!rc) rc = finish_tail(pl, p, mtr, d_ls, d_ts, s, weighted);
-		if (!rc && prof) {
-			if (pl->le.call_end) rc = hip_rc(hipEventRecord(pe[2], S_(s)), "stack: event");
-			pl->prof_used += 3;
-		}
-		pl->le = tspws_hip_plan::LaunchEvents();
-		return rc;
 	}
-	rc = tspws_hip_stack_local(pl, p, d_x, ld, mtr, 0, mtr, s);
-	if (!rc) {
-		if (prof && (!ride || pl->le.last_stop)) rc = hip_rc(hipEventRecord(pe[1], S_(s)), "stack: event");
-		if (!rc && prof && pl->le.first_start) rc = hip_rc(hipEventRecord(pe[0], S_(s)), "stack: event"); // (never: both are consumed together)
-		pl->le.first_start = pl->le.last_stop = nullptr;
-		pl->le.call_end = prof ? pe[2] : nullptr;
-	}
-	if (!rc) rc = tspws_hip_stack_finish(pl, p, mtr, d_ls, d_ts, s);
+	if (!rc && prof && (!ride || pl->le.last_stop)) rc = hip_rc(hipEventRecord(pe[1], S_(s)), "stack: event");
+	if (!rc && prof && pl->le.first_start) rc = hip_rc(hipEventRecord(pe[0], S_(s)), "stack: event"); // (never: both are consumed together)
+	pl->le.first_start = pl->le.last_stop = nullptr;
+	pl->le.call_end = (!rc && prof) ? pe[2] : nullptr;
+	if (!rc) rc = ride ? tspws_hip_stack_finish(pl, p, mtr, d_ls, d_ts, s) : finish_tail(pl, p, mtr, d_ls, d_ts, s, weighted);
 	if (!rc && prof) {
 		if (pl->le.call_end) rc = hip_rc(hipEventRecord(pe[2], S_(s)), "stack: event");
 		pl->prof_used += 3;

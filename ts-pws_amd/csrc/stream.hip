@@ -534,7 +534,7 @@ static int chunk_tables(tspws_hip_plan *p, const std::vector<Chunk> &chunks, con
 	if (nck) HIP_TRY(hipMemcpyAsync(*d_chunks, chunks.data(), nck * sizeof(Chunk), hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemcpyAsync(*d_rf, row_first.data(), (rows + 1) * sizeof(unsigned), hipMemcpyHostToDevice, st));
 	if (cached) {
-		if (!p->ck_ev) HIP_TRY(hipEventCreateWithFlags(&p->ck_ev, hipEventDisableTiming));
+		if ((rc = tspws_plan_event(p->ck_ev, true))) return rc;
 		HIP_TRY(hipEventRecord(p->ck_ev, st));
 		p->ck_stream = st;
 		p->ck_dev = true; // only now: a failed upload must not leave a table that looks valid

@@ -8,6 +8,7 @@
 //   inverse.hip   phase weighting, inverse frame CWT (inv_poly.h), epilogue
 //   stack.hip     the whole call on device-resident traces: local half, finish stage (whole / in pieces / by scales)
 //   resample.hip  jackknife, random subsampling, convergence curves
+//   spectral.hip  the far-decimated octaves through the traces' spectra (spectral.h)
 //   jk_single.hip single-stage jackknife from per-class stacks
 //   batch.hip     many same-length ensembles in one call
 //   comm.hip      trace shards on several devices of one process: RCCL all-reduce, sharded tspws_main driver
@@ -17,8 +18,9 @@
 //   partials     double  [Kmax][ldP]   stage-1 group sums of the two-stage stack
 //   taps         double2 [ntaps]       ragged per scale, tap_off[s] .. ; dual taps likewise
 //   coefficients double2 [ncoef]       ragged [S][N_s], coef_off[s] ..  (N_s = ceil(N/D_s))
-// All arithmetic on the path is FP64 (the reference is double / double complex throughout); MFMA is deliberately unused:
-// the per-scale FIRs are skinny 1-D correlations.  Reference citations are relative to /root/reference/src.
+// All arithmetic on the path is FP64 (the reference is double / double complex throughout).  The per-scale FIRs are skinny 1-D
+// correlations on the vector units; the FP64 matrix pipe (MFMA) takes the fold of the spectral chain (spectral.hip) and the dense
+// contraction of the coarsest scales (fwd_gemm.h).  Reference citations are relative to /root/reference/src.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -233,7 +235,7 @@ struct tspws_hip_plan {
 	void *scr[SCR_N] = {nullptr};
 	size_t scr_bytes[SCR_N] = {0};
 	// forward transform: the direct kernel (coarse scales, latency-bound) runs beside the LDS kernel (FP64-bound) on a
-	// side stream, forked from and joined back into the caller's stream
+	// side stream, forked from and joined back into the caller's stream (tspws_fork / tspws_join, plan.hip)
 	hipStream_t side = nullptr;
 	hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 	hipStream_t xs = nullptr;          // ... and the spectral chain of a few-row launch beside both (forward.hip)
@@ -275,6 +277,12 @@ struct tspws_hip_plan {
 
 int tspws_scratch(tspws_hip_plan *p, int slot, size_t bytes, void **out);
 #define scratch tspws_scratch
+// the plan's side streams (s: p->side, p->xs or p->xf) and ordering events (e: any event of the plan), created on first use -- here only
+int tspws_plan_stream(tspws_hip_plan *p, hipStream_t &s);
+int tspws_plan_event(hipEvent_t &e, bool system_scope = false);
+// fork: `side` waits for what is enqueued on `from` -- for `carried` when a launch on `from` already signals that event, else for ev, recorded here
+int tspws_fork(tspws_hip_plan *p, hipStream_t from, hipStream_t &side, hipEvent_t &ev, hipEvent_t carried = nullptr);
+int tspws_join(hipStream_t side, hipStream_t into, hipEvent_t &ev); // `into` waits for what is enqueued on `side` (ev recorded there)
 
 // ------------------------------------------------------------------------------------------
 // device helpers shared by the kernels of several units
@@ -351,19 +359,20 @@ __device__ __forceinline__ double2 weight_value(const double2 st, const double2 
 // ------------------------------------------------------------------------------------------
 // forward.hip
 int  tspws_build_forward(tspws_hip_plan *p);              // work decomposition of the forward kernels (few-trace and many-trace tables)
-int  tspws_forward_parts_f32(tspws_hip_plan *p, const float *d_x, size_t ntr, size_t ld, double2 *d_part, hipStream_t st, FuseOut *fz, ScaleRange rg);
-int  tspws_forward_parts_f64(tspws_hip_plan *p, const double *d_x, size_t ntr, size_t ld, double2 *d_part, hipStream_t st, FuseOut *fz, ScaleRange rg);
+// (templates on the trace type -- float traces, double partial stacks -- are instantiated in the unit that defines them, for the types that have a caller)
+template <typename TIn>
+int  tspws_forward_parts(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t ld, double2 *d_part, hipStream_t st, FuseOut *fz, ScaleRange rg);
 // many-trace pass: engine and decomposition by ntr traces, batches for nslots; then the transforms of one batch of nb traces at xb
-int  tspws_tl_pass_setup_f32(tspws_hip_plan *p, size_t ntr, size_t nslots, TlPass *P);
-int  tspws_tl_pass_transform_f32(tspws_hip_plan *p, const TlPass *P, const float *xb, size_t ld, unsigned nb, hipStream_t st);
-int  tspws_join_fir_stream(tspws_hip_plan *p, hipStream_t fir, hipStream_t st); // FuseOut::defer_fir_join: st waits for what is enqueued on fir
+template <typename TIn>
+int  tspws_tl_pass_setup(tspws_hip_plan *p, size_t ntr, size_t nslots, TlPass &P);
+template <typename TIn>
+int  tspws_tl_pass_transform(tspws_hip_plan *p, const TlPass &P, const TIn *xb, size_t ld, unsigned nb, hipStream_t st);
 // ST / PS of ntr traces (keep: add to the stacks already there; wa: weighting applied by the launch that completes the
 // stacks, *weighted tells whether that happened; rg: only these scales)
-int  tspws_stacks_f32(tspws_hip_plan *p, const float *d_x, size_t ntr, size_t ld, double *d_ST, double *d_PS, hipStream_t st, bool keep,
-                      const WeightArgs *wa, bool *weighted, ScaleRange rg);
+template <typename TIn>
+int  tspws_stacks(tspws_hip_plan *p, const TIn *d_x, size_t ntr, size_t ld, double *d_ST, double *d_PS, hipStream_t st, bool keep,
+                  const WeightArgs *wa, bool *weighted, ScaleRange rg);
 unsigned tspws_first_unfused_scale(const tspws_hip_plan *p); // scales [it, S) hold every scale the fused forward kernel does not stack itself
-int  tspws_stacks_f64(tspws_hip_plan *p, const double *d_x, size_t ntr, size_t ld, double *d_ST, double *d_PS, hipStream_t st, bool keep,
-                      const WeightArgs *wa, bool *weighted, ScaleRange rg);
 // k_accumulate_parts for nb transformed traces (nbatch independent stacks side by side: y_part / y_stack apart)
 void tspws_launch_accumulate(tspws_hip_plan *p, const double2 *part, unsigned nb, double2 *ST, double2 *PS, int zero_first, const FuseOut *fz,
                              unsigned nslices, hipStream_t st, unsigned nbatch, size_t y_part, size_t y_stack, const TlTable *tl, const WeightArgs *wa,
@@ -382,11 +391,13 @@ int  tspws_spectral_rows_f64(tspws_hip_plan *p, SpecDecomp *dc, const double *d_
 int  tspws_build_tl_spectral(tspws_hip_plan *p, unsigned s_first, unsigned s_end, unsigned nblk_hint, TlTable &T); // (forward.hip) scale table + trace-lane items of that decomposition
 void tspws_spectral_geometry(const tspws_hip_plan *p, unsigned *NT, unsigned *s_end, unsigned *cneg); // transform length, end of the scales that fit its window, samples in front of the trace
 unsigned tspws_spectral_end_scale(const tspws_hip_plan *p); // end of the spectral set (S unless the coarsest filters do not fit the transform window)
-int  tspws_spectral_run_f32(tspws_hip_plan *p, SpecDecomp *dc, const float *xT, unsigned TP, unsigned ntr, double2 *ST, double2 *PS, size_t stride, double2 *Y, hipStream_t st);
-int  tspws_spectral_run_f64(tspws_hip_plan *p, SpecDecomp *dc, const double *xT, unsigned TP, unsigned ntr, double2 *ST, double2 *PS, size_t stride, double2 *Y, hipStream_t st);
+struct SpecRowsOut; // (few rows in columns: spectral.hip's own)
+template <typename TIn>
+int  tspws_spectral_run(tspws_hip_plan *p, SpecDecomp *dc, const TIn *xT, unsigned TP, unsigned ntr, double2 *ST, double2 *PS, size_t stride, double2 *Y, hipStream_t st,
+                        const SpecRowsOut *ro = nullptr, unsigned tps = 0, unsigned ncol = 0);
 // the batch transposed (xT[n][t], TP = padded trace count) + the traces' largest |sample| where the spectral chain looks for them
-int  tspws_spectral_transpose_f32(tspws_hip_plan *p, const float *d_x, size_t ld, unsigned ntr, float *xT, unsigned TP, hipStream_t st);
-int  tspws_spectral_transpose_f64(tspws_hip_plan *p, const double *d_x, size_t ld, unsigned ntr, double *xT, unsigned TP, hipStream_t st);
+template <typename TIn>
+int  tspws_spectral_transpose(tspws_hip_plan *p, const TIn *d_x, size_t ld, unsigned ntr, TIn *xT, unsigned TP, hipStream_t st);
 void tspws_spectral_destroy(tspws_hip_plan *p);
 // inverse.hip
 int  tspws_build_inverse(tspws_hip_plan *p);
