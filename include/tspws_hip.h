@@ -264,6 +264,35 @@ int  tspws_selection_classes(const char *sel, unsigned C, size_t mtr, unsigned *
 int  tspws_hip_jackknife_single(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, size_t mtr,
                                 const char *h_sel, unsigned C, float *d_ls_out, float *d_ts_out, unsigned *h_mtr_out, void *stream);
 
+/* The single-stage jackknife of B ensembles of one trace array in ONE call.  Ensemble b is the traces [h_first[b], h_first[b+1]) of d_sigall
+ * (the rules of tspws_hip_stack_batch: B + 1 non-decreasing host entries, h_first[0] may be > 0).  h_sel is [C][T] bytes (1 = kept), T =
+ * h_first[B] - h_first[0]: column i - h_first[0] belongs to trace i, every ensemble has the same C; the caller builds each ensemble's columns
+ * with tspws_jackknife_plan on that ensemble's own start times (any 0/1 matrix is accepted).  The replica block [b][C][max] of d_ls_out /
+ * d_ts_out and h_mtr_out[b][C] receive what tspws_hip_jackknife_single gives for ensemble b alone with its columns (K_c = 0: zero rows, count
+ * 0), row b of d_ls / d_tsPWS ([B][max]; both NULL: not wanted) what tspws_hip_stack_batch writes for it (weights with K = M = M_b, ls by
+ * a float division by M_b), to the parity tolerance (relerr 2e-6).  An empty ensemble gives zero rows and zero counts.  Single-stage parameter
+ * sets only: tspws_is_two_stage for any ensemble returns TSPWS_E_ARG (tspws_hip_jackknife is the two-stage route), and so do NULL plan / p /
+ * h_first / h_sel / replica outputs / h_mtr_out, exactly one of d_ls / d_tsPWS NULL, decreasing offsets, ld < max and more than 65535 classes
+ * (distinct selection columns) in one ensemble -- all before any device work.  B == 0 or C == 0 returns 0 and does nothing.  Fold and mean
+ * removal stay with the caller.  When the total trace count takes the many-trace path, every (ensemble, class) starts a fresh 64-trace block
+ * of ONE shared pass in which every trace is transformed once, and every replica is a sum of its ensemble's class planes; otherwise the call
+ * is one tspws_hip_stack + tspws_hip_jackknife_single per ensemble.  Every scratch block that grows with the ensembles stays within
+ * TSPWS_PART_MB (rounds of whole ensembles; one ensemble alone may exceed it).  The call uploads host tables and waits for `stream`: on
+ * return the outputs are complete. */
+int  tspws_hip_jackknife_batch(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, const size_t *h_first, unsigned B,
+                               const char *h_sel, unsigned C, float *d_ls, float *d_tsPWS, float *d_ls_out, float *d_ts_out,
+                               unsigned *h_mtr_out, void *stream);
+/* How the plan's last tspws_hip_jackknife_batch call with B > 0 and C > 0 went (all zero before the first one). */
+typedef struct {
+	unsigned shared;       /* ensembles that went through the shared many-trace pass                            */
+	unsigned looped;       /* ensembles finished by one tspws_hip_stack + tspws_hip_jackknife_single each       */
+	unsigned empty;        /* ensembles without traces (zero rows, zero counts)                                 */
+	unsigned rounds;       /* rounds forced by the scratch budget (a round never splits an ensemble)            */
+	unsigned pass_batches; /* batches of the many-trace pass (a class may straddle two)                         */
+	unsigned classes;      /* (ensemble, class) segments in total                                               */
+} tspws_hip_jk_batch_stats;
+int  tspws_hip_jackknife_batch_stats(const tspws_hip_plan *plan, tspws_hip_jk_batch_stats *stats);
+
 /* ---- random subsampling ---------------------------------------------------------------------- */
 /* Host: keep K of J traces at random with libc rand(), flipping whichever symbol is rarer.
  * SubsamplingPlan, ts_pws1f_lib.c:355-383 (same rand() call order, so the same masks from the same state). */

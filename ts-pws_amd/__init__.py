@@ -126,6 +126,8 @@ SYMBOLS = {
     "tspws_hip_jackknife_finish": (_i, [_vp, _vp, _sz, _vp, _u, _u, _u, _vp, _vp, _vp, _vp]),
     "tspws_selection_classes": (_i, [_vp, _u, _sz, _vp, _vp, C.POINTER(_u)]),
     "tspws_hip_jackknife_single": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _u, _vp, _vp, _vp, _vp]),
+    "tspws_hip_jackknife_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tspws_hip_jackknife_batch_stats": (_i, [_vp, _vp]),
     "tspws_subsampling_plan": (_i, [_vp, _sz, _sz]),
     "tspws_hip_subsample": (_i, [_vp, _vp, _vp, _sz, _sz, _u, _vp, _vp, _vp]),
     "tspws_hip_subsample_sel": (_i, [_vp, _vp, _vp, _sz, _sz, _u, _vp, _vp, _vp, _vp]),
@@ -471,6 +473,55 @@ class Plan:
         check(self.lib.tspws_hip_stack_batch_stats(self.h, C.byref(st)), "stack_batch_stats")
         return dict(zip(("single_pass", "two_stage_pass", "looped", "empty", "rounds", "pass_batches"), list(st)))
 
+    def jackknife_batch(self, traces, first, sel, ls=None, ts=None, ls_out=None, ts_out=None, mtr_out=None, main=True):
+        """Single-stage jackknife of B ensembles of one trace array in ONE call (tspws_hip_jackknife_batch): ensemble b = rows
+        [first[b], first[b+1]) of the float32 [mtr][N] device tensor `traces`; `sel` = [C][T] int8 selection, T = first[B] - first[0], column
+        i - first[0] for trace i (jackknife_selection_batch).  Returns ls[B][N], ts[B][N] (the plain stacks, as stack_batch; None with
+        main=False), jk_ls[B][C][N], jk_ts[B][C][N] (float32 cuda) and jk_mtr[B][C] (uint32): block b = what jackknife_single gives for
+        ensemble b alone (an empty ensemble: zero rows and counts)."""
+        import numpy as np
+        import torch
+        mtr, ld = self._traces(traces)
+        f = np.asarray(first)
+        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
+            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
+        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
+            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
+        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
+        B, T = f.size - 1, int(f[-1] - f[0])
+        if not isinstance(sel, np.ndarray) or sel.ndim != 2 or sel.dtype not in (np.int8, np.uint8, np.bool_):
+            raise TspwsError("selection must be a 2-D int8 / uint8 / bool numpy array [C][T]")
+        sel = self._sel(sel, sel.shape[0], T)
+        Cn = sel.shape[0]
+        dev = traces.device
+        if main:
+            ls = torch.empty((B, self.N), dtype=torch.float32, device=dev) if ls is None else ls
+            ts = torch.empty((B, self.N), dtype=torch.float32, device=dev) if ts is None else ts
+        elif ls is not None or ts is not None:
+            raise TspwsError("main=False takes no ls / ts")
+        ls_out = torch.empty((B, Cn, self.N), dtype=torch.float32, device=dev) if ls_out is None else ls_out
+        ts_out = torch.empty((B, Cn, self.N), dtype=torch.float32, device=dev) if ts_out is None else ts_out
+        mtr_out = np.zeros((B, Cn), np.uint32) if mtr_out is None else mtr_out
+        if not isinstance(mtr_out, np.ndarray) or mtr_out.dtype != np.uint32 or mtr_out.shape != (B, Cn) or not mtr_out.flags.c_contiguous:
+            raise TspwsError(f"mtr_out must be a contiguous uint32 numpy array [{B}][{Cn}]")
+        checks = [(ls_out, "ls_out", (B, Cn, self.N)), (ts_out, "ts_out", (B, Cn, self.N))]
+        if main:
+            checks += [(ls, "ls", (B, self.N)), (ts, "ts", (B, self.N))]
+        for t, name, shape in checks:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda or \
+                    (t.device.index or 0) != self.device:
+                raise TspwsError(f"{name} must be a contiguous float32 {list(shape)} tensor on cuda:{self.device}")
+        check(self.lib.tspws_hip_jackknife_batch(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, sel.ctypes.data, Cn,
+                                                 ls.data_ptr() if main else None, ts.data_ptr() if main else None, ls_out.data_ptr(),
+                                                 ts_out.data_ptr(), mtr_out.ctypes.data, self._stream()), "jackknife_batch")
+        return ls, ts, ls_out, ts_out, mtr_out
+
+    def jackknife_batch_stats(self):
+        """How the last jackknife_batch call with B > 0 and C > 0 went (tspws_hip_jackknife_batch_stats): dict of counts."""
+        st = (C.c_uint * 6)()
+        check(self.lib.tspws_hip_jackknife_batch_stats(self.h, C.byref(st)), "jackknife_batch_stats")
+        return dict(zip(("shared", "looped", "empty", "rounds", "pass_batches", "classes"), list(st)))
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.tspws_hip_plan_destroy(self.h)
@@ -694,6 +745,30 @@ def jackknife_selection(times, n, d):
     rc = load().tspws_jackknife_plan(sel.ctypes.data, times.ctypes.data, times.size, d, n, Cn)
     if rc:
         raise TspwsError("jackknife_selection: no trace start times" if rc == -2 else f"jackknife_selection failed with code {rc}")
+    return sel
+
+
+def jackknife_selection_batch(times, first, n, d):
+    """Delete-d jackknife selection [C][T] (int8, 1 = kept) of B ensembles for Plan.jackknife_batch: times[i] = start time of trace i,
+    ensemble b = traces [first[b], first[b+1]), T = first[B] - first[0]; the columns of every ensemble come from one tspws_jackknife_plan call
+    on that ensemble's own start times (an empty ensemble has no columns).  Raises when an ensemble's first start time is 0."""
+    import math
+    import numpy as np
+    times = np.ascontiguousarray(times, dtype=np.int64)
+    f = np.asarray(first)
+    if times.ndim != 1 or f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
+        raise TspwsError("times must be 1-D start times and first a 1-D integer array of B + 1 ensemble offsets")
+    if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > times.size:
+        raise TspwsError(f"first must be non-decreasing offsets into the {times.size} start times")
+    if not 0 < d < n:
+        raise TspwsError(f"jackknife needs 0 < d < n, got n = {n}, d = {d}")
+    Cn = math.comb(n, d)
+    f0 = int(f[0])
+    sel = np.zeros((Cn, int(f[-1]) - f0), np.int8)
+    for b in range(f.size - 1):
+        a, e = int(f[b]), int(f[b + 1])
+        if e > a:
+            sel[:, a - f0:e - f0] = jackknife_selection(times[a:e], n, d)
     return sel
 
 

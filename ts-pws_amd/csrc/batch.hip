@@ -20,18 +20,9 @@
 // Batches that the many-trace rule would not take as a whole, and a batch with a single ensemble of its kind, fall back to one
 // tspws_hip_stack per ensemble.  tspws_hip_stack_batch_stats tells which way the last call's ensembles went.
 #include "tspws_internal.h"
+#include "batch_kernels.h"
 
 #define is_two_stage tspws_is_two_stage
-
-// slot j of a gathered batch = trace src[j] of x (row stride ld); src[j] < 0: an idle lane of an ensemble's last block (zeros)
-__global__ void __launch_bounds__(256) k_batch_gather(const float *__restrict__ x, size_t ld, const long long *__restrict__ src, unsigned N,
-                                                      float *__restrict__ xg)
-{
-	const unsigned n = blockIdx.x * 256 + threadIdx.x;
-	if (n >= N) return;
-	const long long t = src[blockIdx.y];
-	xg[(size_t)blockIdx.y * N + n] = t >= 0 ? x[(size_t)t * ld + n] : 0.f;
-}
 
 // k_epilogue for a round of stacks: rows 2j / 2j + 1 of x are ICWT(OUT) / ICWT(ST) of stack j = blockIdx.y; its outputs go to row[j] of
 // ls / ts, ls by a FLOAT division by the stack's trace count (ts_pws1f_lib.c:233-241)

@@ -14,6 +14,7 @@
 // FP64 summation order: by class, then over the kept classes in class order (not trace order); the float outputs agree with a
 // trace-order restatement to the last bits.  A replica without traces (K_c = 0) gets zero rows and count 0.
 #include "tspws_internal.h"
+#include "batch_kernels.h"
 #include <string>
 #include <unordered_map>
 
@@ -87,32 +88,6 @@ __global__ void __launch_bounds__(256) k_j1_accumulate(const double2 *__restrict
 	}
 	ST[i] = st;
 	PS[i] = ps;
-}
-
-// FP64 time-domain sum of every class (blockIdx.y): T[k][n] = sum over its traces in trace order of (double) x[i][n]
-__global__ void __launch_bounds__(256) k_j1_time(const float *__restrict__ x, size_t ld, size_t N, const unsigned *__restrict__ idx,
-                                                 const unsigned *__restrict__ cptr, double *__restrict__ T)
-{
-	const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
-	if (n >= N) return;
-	const unsigned q1 = cptr[blockIdx.y + 1];
-	double acc = 0;
-	for (unsigned q0 = cptr[blockIdx.y]; q0 < q1; q0 += 8) { // eight rows' loads in flight
-		float v[8];
-#pragma unroll
-		for (int j = 0; j < 8; j++) v[j] = q0 + (unsigned)j < q1 ? x[(size_t)idx[q0 + j] * ld + n] : 0.f;
-#pragma unroll
-		for (int j = 0; j < 8; j++) if (q0 + (unsigned)j < q1) acc += (double)v[j];
-	}
-	T[(size_t)blockIdx.y * N + n] = acc;
-}
-
-__device__ __forceinline__ int j1_weight_mode(double wu, int unbiased, unsigned K) // tspws_weight_mode (inverse.hip), per replica
-{
-	if (wu == 2 && unbiased && K != 1) return 3;
-	if (wu == 2) return 0;
-	if (wu == 1) return 1;
-	return 2;
 }
 
 static constexpr unsigned J1_NT = 64;      // coefficients per workgroup of k_j1_finish

@@ -11,6 +11,7 @@
 //   spectral.hip  the far-decimated octaves through the traces' spectra (spectral.h)
 //   jk_single.hip single-stage jackknife from per-class stacks
 //   batch.hip     many same-length ensembles in one call
+//   jk_batch.hip  single-stage jackknife of many ensembles in one call (batch_kernels.h: the small kernels those three share)
 //   comm.hip      trace shards on several devices of one process: RCCL all-reduce, sharded tspws_main driver
 //
 // Layout in HBM
@@ -174,7 +175,7 @@ struct AccExtra {
 	bool fused_done = false;          // the fused forward kernel completed (and weighted) the stacks of its scales itself: only the others are left
 };
 
-enum { SCR_Y = 0, SCR_PART, SCR_XT, SCR_OBUF, SCR_SEL, SCR_SUBST, SCR_CONV, SCR_CHUNK, SCR_P, SCR_STPS, SCR_OUT, SCR_X2, SCR_CLS, SCR_JKP, SCR_JKOUT, SCR_TAB, SCR_FZ, SCR_JKTAB, SCR_SPA, SCR_SPB, SCR_SPG, SCR_SPH, SCR_SPM, SCR_SPK, SCR_GEMM, SCR_J1TAB, SCR_J1PL, SCR_J1T, SCR_BTAB, SCR_BXG, SCR_BY, SCR_BX, SCR_BP, SCR_N };
+enum { SCR_Y = 0, SCR_PART, SCR_XT, SCR_OBUF, SCR_SEL, SCR_SUBST, SCR_CONV, SCR_CHUNK, SCR_P, SCR_STPS, SCR_OUT, SCR_X2, SCR_CLS, SCR_JKP, SCR_JKOUT, SCR_TAB, SCR_FZ, SCR_JKTAB, SCR_SPA, SCR_SPB, SCR_SPG, SCR_SPH, SCR_SPM, SCR_SPK, SCR_GEMM, SCR_J1TAB, SCR_J1PL, SCR_J1T, SCR_BTAB, SCR_BXG, SCR_BY, SCR_BX, SCR_BP, SCR_JBTAB, SCR_JBPL, SCR_JBT, SCR_JBY, SCR_JBX, SCR_N };
 
 struct OctDesc; // inverse work items (inv_poly.h)
 struct TLItem;  // many-trace forward work items (fwd_tl.h)
@@ -273,6 +274,7 @@ struct tspws_hip_plan {
 	// until plan_destroy
 	std::vector<void *> retired;
 	tspws_hip_batch_stats batch_stats{}; // how the last batched call (batch.hip) stacked its ensembles
+	tspws_hip_jk_batch_stats jk_batch_stats{}; // ... and the last batched jackknife (jk_batch.hip)
 };
 
 int tspws_scratch(tspws_hip_plan *p, int slot, size_t bytes, void **out);
