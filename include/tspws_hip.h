@@ -293,6 +293,40 @@ typedef struct {
 } tspws_hip_jk_batch_stats;
 int  tspws_hip_jackknife_batch_stats(const tspws_hip_plan *plan, tspws_hip_jk_batch_stats *stats);
 
+/* The TWO-stage jackknife (TwoStage_jackknife_float, :719-831) of B ensembles of one trace array in ONE call.  Arguments as
+ * tspws_hip_jackknife_batch: h_first has B + 1 non-decreasing host entries (h_first[0] may be > 0), ld > max is allowed, h_sel is [C][T]
+ * bytes (1 = kept; any 0/1 matrix), T = h_first[B] - h_first[0].  The replica block [b][C][max] of d_ls_out / d_ts_out and h_mtr_out[b][C]
+ * receive what tspws_hip_jackknife gives for ensemble b alone with its columns: the group of a selected trace is floor(k Kmax / K_c), k its
+ * rank among the selected traces (:766); tsPWS_out = (float) Re_rec(weight(ST_c, PS_c; K = Kmax, M = K_c)); ls_out = (float)((sum of the
+ * groups' partial stacks) * (1 / K_c)), formed in the time domain (:799-811); h_mtr_out = K_c.  A replica with 0 < K_c < Kmax has empty
+ * groups, whose rows count as zero (as in the reference); K_c = 0 gives zero rows and count 0 (the batch calls' choice: the single call
+ * divides by zero there).  Row b of d_ls / d_tsPWS ([B][max]; both NULL: not wanted) is what tspws_hip_stack_batch writes for the ensemble
+ * (weights with (Kmax, M_b), ls by a float division by M_b).  All to the parity tolerance (relerr 2e-6).  An empty ensemble gives zero
+ * rows and zero counts.  Two-stage parameter sets only: a non-empty ensemble that is not two-stage by tspws_is_two_stage (Kmax == 0 or
+ * Kmax > M_b) returns TSPWS_E_ARG ("single-stage": tspws_hip_jackknife_batch is that route), and so do NULL plan / p / h_first / h_sel /
+ * replica outputs / h_mtr_out, exactly one of d_ls / d_tsPWS NULL, decreasing offsets and ld < max -- all before any device work, outputs
+ * untouched.  B == 0 or C == 0 returns 0 and does nothing.  Fold and mean removal stay with the caller.
+ * With ONE non-empty ensemble the call IS tspws_hip_stack_jackknife for it (tspws_hip_jackknife without the main rows), bit for bit.  With
+ * two or more, one streaming kernel walks every ensemble's traces once: a workgroup owns one (ensemble, tile of <= 16 columns, 1024 samples),
+ * keeps a running FP64 sum per column in registers and stores the Kmax partial-stack rows of every column (replicas and, as the last column
+ * of the last tile, the plain stack) -- no atomics, every row written by one workgroup; then one forward launch over all rows of the round,
+ * one accumulation, the weights with each column's trace count, the replicas' linear stacks, one batched inverse and the float epilogue.
+ * Every scratch block that grows with the ensembles stays within TSPWS_PART_MB (rounds of whole ensembles; one ensemble alone may exceed
+ * it).  The call uploads one table block per round and waits for `stream`: on return the outputs are complete. */
+int  tspws_hip_jackknife_batch_two_stage(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, const size_t *h_first,
+                                         unsigned B, const char *h_sel, unsigned C, float *d_ls, float *d_tsPWS, float *d_ls_out,
+                                         float *d_ts_out, unsigned *h_mtr_out, void *stream);
+/* How the plan's last tspws_hip_jackknife_batch_two_stage call with B > 0 and C > 0 went (all zero before the first one). */
+typedef struct {
+	unsigned shared;       /* ensembles that went through the shared walk                                       */
+	unsigned looped;       /* 1: the only non-empty ensemble went through tspws_hip_stack_jackknife / _jackknife */
+	unsigned empty;        /* ensembles without traces (zero rows, zero counts)                                 */
+	unsigned rounds;       /* rounds forced by the scratch budget (a round never splits an ensemble)            */
+	unsigned tiles;        /* column tiles (of <= 16 columns) per ensemble                                      */
+	unsigned rows;         /* partial-stack rows transformed in total                                           */
+} tspws_hip_jk_batch2_stats;
+int  tspws_hip_jackknife_batch_two_stage_stats(const tspws_hip_plan *plan, tspws_hip_jk_batch2_stats *stats);
+
 /* ---- random subsampling ---------------------------------------------------------------------- */
 /* Host: keep K of J traces at random with libc rand(), flipping whichever symbol is rarer.
  * SubsamplingPlan, ts_pws1f_lib.c:355-383 (same rand() call order, so the same masks from the same state). */

@@ -128,6 +128,8 @@ SYMBOLS = {
     "tspws_hip_jackknife_single": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _u, _vp, _vp, _vp, _vp]),
     "tspws_hip_jackknife_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_jackknife_batch_stats": (_i, [_vp, _vp]),
+    "tspws_hip_jackknife_batch_two_stage": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tspws_hip_jackknife_batch_two_stage_stats": (_i, [_vp, _vp]),
     "tspws_subsampling_plan": (_i, [_vp, _sz, _sz]),
     "tspws_hip_subsample": (_i, [_vp, _vp, _vp, _sz, _sz, _u, _vp, _vp, _vp]),
     "tspws_hip_subsample_sel": (_i, [_vp, _vp, _vp, _sz, _sz, _u, _vp, _vp, _vp, _vp]),
@@ -473,12 +475,8 @@ class Plan:
         check(self.lib.tspws_hip_stack_batch_stats(self.h, C.byref(st)), "stack_batch_stats")
         return dict(zip(("single_pass", "two_stage_pass", "looped", "empty", "rounds", "pass_batches"), list(st)))
 
-    def jackknife_batch(self, traces, first, sel, ls=None, ts=None, ls_out=None, ts_out=None, mtr_out=None, main=True):
-        """Single-stage jackknife of B ensembles of one trace array in ONE call (tspws_hip_jackknife_batch): ensemble b = rows
-        [first[b], first[b+1]) of the float32 [mtr][N] device tensor `traces`; `sel` = [C][T] int8 selection, T = first[B] - first[0], column
-        i - first[0] for trace i (jackknife_selection_batch).  Returns ls[B][N], ts[B][N] (the plain stacks, as stack_batch; None with
-        main=False), jk_ls[B][C][N], jk_ts[B][C][N] (float32 cuda) and jk_mtr[B][C] (uint32): block b = what jackknife_single gives for
-        ensemble b alone (an empty ensemble: zero rows and counts)."""
+    def _jackknife_batch(self, what, traces, first, sel, ls, ts, ls_out, ts_out, mtr_out, main):
+        """Argument checks, output allocation and the call of the batched jackknives (tspws_hip_<what>)."""
         import numpy as np
         import torch
         mtr, ld = self._traces(traces)
@@ -511,16 +509,37 @@ class Plan:
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda or \
                     (t.device.index or 0) != self.device:
                 raise TspwsError(f"{name} must be a contiguous float32 {list(shape)} tensor on cuda:{self.device}")
-        check(self.lib.tspws_hip_jackknife_batch(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, sel.ctypes.data, Cn,
-                                                 ls.data_ptr() if main else None, ts.data_ptr() if main else None, ls_out.data_ptr(),
-                                                 ts_out.data_ptr(), mtr_out.ctypes.data, self._stream()), "jackknife_batch")
+        check(getattr(self.lib, "tspws_hip_" + what)(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, sel.ctypes.data, Cn,
+                                                     ls.data_ptr() if main else None, ts.data_ptr() if main else None, ls_out.data_ptr(),
+                                                     ts_out.data_ptr(), mtr_out.ctypes.data, self._stream()), what)
         return ls, ts, ls_out, ts_out, mtr_out
+
+    def jackknife_batch(self, traces, first, sel, ls=None, ts=None, ls_out=None, ts_out=None, mtr_out=None, main=True):
+        """Single-stage jackknife of B ensembles of one trace array in ONE call (tspws_hip_jackknife_batch): ensemble b = rows
+        [first[b], first[b+1]) of the float32 [mtr][N] device tensor `traces`; `sel` = [C][T] int8 selection, T = first[B] - first[0], column
+        i - first[0] for trace i (jackknife_selection_batch).  Returns ls[B][N], ts[B][N] (the plain stacks, as stack_batch; None with
+        main=False), jk_ls[B][C][N], jk_ts[B][C][N] (float32 cuda) and jk_mtr[B][C] (uint32): block b = what jackknife_single gives for
+        ensemble b alone (an empty ensemble: zero rows and counts)."""
+        return self._jackknife_batch("jackknife_batch", traces, first, sel, ls, ts, ls_out, ts_out, mtr_out, main)
 
     def jackknife_batch_stats(self):
         """How the last jackknife_batch call with B > 0 and C > 0 went (tspws_hip_jackknife_batch_stats): dict of counts."""
         st = (C.c_uint * 6)()
         check(self.lib.tspws_hip_jackknife_batch_stats(self.h, C.byref(st)), "jackknife_batch_stats")
         return dict(zip(("shared", "looped", "empty", "rounds", "pass_batches", "classes"), list(st)))
+
+    def jackknife_batch_two_stage(self, traces, first, sel, ls=None, ts=None, ls_out=None, ts_out=None, mtr_out=None, main=True):
+        """Two-stage jackknife of B ensembles of one trace array in ONE call (tspws_hip_jackknife_batch_two_stage); arguments and return
+        tuple as jackknife_batch.  Block b of jk_ls / jk_ts / jk_mtr = what the two-stage tspws_hip_jackknife gives for ensemble b alone with
+        its columns of `sel` (K_c = 0: zero rows, count 0), row b of ls / ts = what stack_batch gives for it (None with main=False).  Every
+        non-empty ensemble must be two-stage (0 < Kmax <= its traces)."""
+        return self._jackknife_batch("jackknife_batch_two_stage", traces, first, sel, ls, ts, ls_out, ts_out, mtr_out, main)
+
+    def jackknife_batch_two_stage_stats(self):
+        """How the last jackknife_batch_two_stage call with B > 0 and C > 0 went (tspws_hip_jackknife_batch_two_stage_stats): dict of counts."""
+        st = (C.c_uint * 6)()
+        check(self.lib.tspws_hip_jackknife_batch_two_stage_stats(self.h, C.byref(st)), "jackknife_batch_two_stage_stats")
+        return dict(zip(("shared", "looped", "empty", "rounds", "tiles", "rows"), list(st)))
 
     def close(self):
         if getattr(self, "h", None):
