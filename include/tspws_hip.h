@@ -350,6 +350,35 @@ int  tspws_hip_convergence(tspws_hip_plan *plan, const t_tsPWS *p, const float *
                            const float *d_ref_ts, const float *d_ref_ls, double *h_ts_sim, double *h_ts_misfit,
                            double *h_ls_sim, double *h_ls_misfit, float *d_ts_steps, float *d_ls_steps, void *stream);
 
+/* The convergence curves of B ensembles of one trace array in ONE call.  Ensemble b = the traces [h_first[b], h_first[b+1]) of d_sigall
+ * (the rules of tspws_hip_stack_batch: B + 1 non-decreasing host offsets, h_first[0] may be > 0, ld >= max), T = h_first[B] - h_first[0].
+ * d_ref_ts / d_ref_ls are [B][max] floats on the device: row b is the reference of ensemble b.  Entry i - h_first[0] of the four host
+ * curves ([T] doubles) and row i - h_first[0] of d_ts_steps / d_ls_steps (NULL or [T][max] floats on the device) belong to trace i; the
+ * entries of ensemble b are what tspws_hip_convergence gives for that ensemble alone with rows b of the references:
+ *   ts-PWS step Tr = j + 1 (j = index inside the ensemble): Kmax == 0 or Tr <= Kmax -- trace j is added to the ensemble's running linear /
+ *   phase stacks, weight with K = M = Tr (Tr = 1: the K = 1 rule); otherwise a two-stage stack of the first Tr traces from scratch (row g of
+ *   Kmax partial stacks = the FP64 sum, in trace order, of the traces j' < Tr with floor(j' Kmax / Tr) == g; weight with K = Kmax, M = Tr).
+ *   Then one inverse, sim = sum d r / sqrt(sum d^2) / sqrt(sum r^2), misfit = sum (d - r)^2 against row b of d_ref_ts, (float) d to d_ts_steps.
+ *   linear step: d += x_j; d *= (double)(float)(1.0 / (j + 1)); metrics against row b of d_ref_ls; steps; d *= (j + 1); from zero for every ensemble.
+ * An empty ensemble has no entries.  With exactly one non-empty ensemble the call IS tspws_hip_convergence for it.  B == 0 or T == 0: returns 0
+ * and does nothing.  A NULL plan, p, h_first, d_sigall, reference or host curve, decreasing offsets or ld < max: TSPWS_E_ARG before any device
+ * work, outputs untouched.  Fold and mean removal stay with the caller.  Every sum has a fixed order, nothing is atomic; every scratch block
+ * that grows with T stays within TSPWS_PART_MB (rounds).  The call uploads its tables and waits for `stream`: on return the host arrays are
+ * filled. */
+int  tspws_hip_convergence_batch(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, const size_t *h_first, unsigned B,
+                                 const float *d_ref_ts, const float *d_ref_ls, double *h_ts_sim, double *h_ts_misfit, double *h_ls_sim,
+                                 double *h_ls_misfit, float *d_ts_steps, float *d_ls_steps, void *stream);
+/* How the plan's last tspws_hip_convergence_batch call with traces went (all zero before the first one). */
+typedef struct {
+	unsigned single_steps;    /* incremental steps (Tr <= Kmax, or no two-stage rule)                                  */
+	unsigned two_stage_steps; /* steps recomputed as two-stage stacks (Tr > Kmax)                                      */
+	unsigned rows;            /* partial-stack rows of those steps: Kmax each                                          */
+	unsigned rounds;          /* rounds of incremental steps + rounds of two-stage steps (0 when looped)               */
+	unsigned looped;          /* 1: the only non-empty ensemble went through tspws_hip_convergence                     */
+	unsigned empty;           /* ensembles without traces                                                              */
+} tspws_hip_conv_batch_stats;
+int  tspws_hip_convergence_batch_stats(const tspws_hip_plan *plan, tspws_hip_conv_batch_stats *stats);
+
 /* ---- several devices of one process (single process, ncclCommInitAll, one stream per device) ---------------
  * Traces shard contiguously by global index; what shards is the sum of partial_linear_stacks (ts_pws1f_lib.c:866-881) --
  * single-stage: of ST || PS (:486-494).  The devices' buffers are added by ONE RCCL all-reduce (fp64, sum) over xGMI.

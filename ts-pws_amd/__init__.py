@@ -134,6 +134,8 @@ SYMBOLS = {
     "tspws_hip_subsample": (_i, [_vp, _vp, _vp, _sz, _sz, _u, _vp, _vp, _vp]),
     "tspws_hip_subsample_sel": (_i, [_vp, _vp, _vp, _sz, _sz, _u, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tspws_hip_convergence_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tspws_hip_convergence_batch_stats": (_i, [_vp, _vp]),
     "tspws_hip_synth": (_i, [_vp, _sz, _sz, _sz, C.c_uint64, _sz, _vp]),
     # several devices of one process (csrc/comm.hip)
     "tspws_hip_comm_create": (_i, [C.POINTER(_vp), _i, _vp]),
@@ -540,6 +542,63 @@ class Plan:
         st = (C.c_uint * 6)()
         check(self.lib.tspws_hip_jackknife_batch_two_stage_stats(self.h, C.byref(st)), "jackknife_batch_two_stage_stats")
         return dict(zip(("shared", "looped", "empty", "rounds", "tiles", "rows"), list(st)))
+
+    def _refs(self, t, name, rows):
+        """Data pointer of a reference array: contiguous float32 [rows][N] (or [N] for one row) on the plan's device."""
+        import torch
+        ok = isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda and (t.device.index or 0) == self.device
+        if not ok or (tuple(t.shape) != (rows, self.N) and not (rows == 1 and tuple(t.shape) == (self.N,))):
+            raise TspwsError(f"{name} must be a contiguous float32 [{rows}][{self.N}] tensor on cuda:{self.device}")
+        return t.data_ptr()
+
+    def convergence(self, traces, ref_ts, ref_ls, steps=False):
+        """Convergence curves of ONE ensemble (tspws_hip_convergence) on device tensors: `traces` float32 [mtr][N], `ref_ts` / `ref_ls`
+        float32 [N] references of the ts-PWS / linear curve.  Returns (ts_sim, ts_misfit, ls_sim, ls_misfit) as float64 numpy [mtr]; with
+        steps=True also the [mtr][N] float32 cuda tensors of every step's ts-PWS and linear stack.  Synchronises."""
+        import numpy as np
+        import torch
+        mtr, ld = self._traces(traces)
+        r_ts, r_ls = self._refs(ref_ts, "ref_ts", 1), self._refs(ref_ls, "ref_ls", 1)
+        cur = [np.full(mtr, np.nan) for _ in range(4)]
+        st = [torch.full((mtr, self.N), float("nan"), dtype=torch.float32, device=traces.device) for _ in range(2)] if steps else [None, None]
+        check(self.lib.tspws_hip_convergence(self.h, C.byref(self.params), traces.data_ptr(), ld, mtr, r_ts, r_ls, *[c.ctypes.data for c in cur],
+                                             *[t.data_ptr() if steps else None for t in st], self._stream()), "convergence")
+        return (*cur, *st) if steps else tuple(cur)
+
+    def convergence_batch(self, traces, first, ref_ts=None, ref_ls=None, steps=False):
+        """Convergence curves of B ensembles of one trace array in ONE call (tspws_hip_convergence_batch): ensemble b = rows
+        [first[b], first[b+1]) of the float32 [mtr][N] device tensor `traces`, `first` = B + 1 non-decreasing integer offsets (first[0] may be
+        > 0), T = first[B] - first[0].  `ref_ts` / `ref_ls`: float32 [B][N] cuda, row b = the reference of ensemble b; None (both): the rows of
+        stack_batch(traces, first) -- every ensemble against its own final stacks.  Returns (ts_sim, ts_misfit, ls_sim, ls_misfit) as float64
+        numpy [T], entry i - first[0] for trace i: what `convergence` gives for each ensemble alone; with steps=True also the two [T][N]
+        float32 cuda tensors.  Arrays and tensors hold NaN before the call (an unwritten entry shows).  Synchronises."""
+        import numpy as np
+        import torch
+        mtr, ld = self._traces(traces)
+        f = np.asarray(first)
+        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
+            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
+        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
+            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
+        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
+        B, T = f.size - 1, int(f[-1] - f[0])
+        if (ref_ts is None) != (ref_ls is None):
+            raise TspwsError("ref_ts and ref_ls are given together or not at all")
+        if ref_ts is None:
+            ref_ls, ref_ts = self.stack_batch(traces, f)
+        r_ts, r_ls = self._refs(ref_ts, "ref_ts", B), self._refs(ref_ls, "ref_ls", B)
+        cur = [np.full(T, np.nan) for _ in range(4)]
+        st = [torch.full((T, self.N), float("nan"), dtype=torch.float32, device=traces.device) for _ in range(2)] if steps else [None, None]
+        check(self.lib.tspws_hip_convergence_batch(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, r_ts, r_ls,
+                                                   *[c.ctypes.data for c in cur], *[t.data_ptr() if steps else None for t in st], self._stream()),
+              "convergence_batch")
+        return (*cur, *st) if steps else tuple(cur)
+
+    def convergence_batch_stats(self):
+        """How the last convergence_batch call with traces went (tspws_hip_convergence_batch_stats): dict of counts."""
+        st = (C.c_uint * 6)()
+        check(self.lib.tspws_hip_convergence_batch_stats(self.h, C.byref(st)), "convergence_batch_stats")
+        return dict(zip(("single_steps", "two_stage_steps", "rows", "rounds", "looped", "empty"), list(st)))
 
     def close(self):
         if getattr(self, "h", None):

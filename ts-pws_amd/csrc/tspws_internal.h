@@ -13,6 +13,7 @@
 //   batch.hip     many same-length ensembles in one call
 //   jk_batch.hip  single-stage jackknife of many ensembles in one call (batch_kernels.h: the small kernels those three share)
 //   jk_batch_two_stage.hip  two-stage jackknife of many ensembles in one call
+//   conv_batch.hip  convergence curves of many ensembles in one call
 //   comm.hip      trace shards on several devices of one process: RCCL all-reduce, sharded tspws_main driver
 //
 // Layout in HBM
@@ -176,7 +177,7 @@ struct AccExtra {
 	bool fused_done = false;          // the fused forward kernel completed (and weighted) the stacks of its scales itself: only the others are left
 };
 
-enum { SCR_Y = 0, SCR_PART, SCR_XT, SCR_OBUF, SCR_SEL, SCR_SUBST, SCR_CONV, SCR_CHUNK, SCR_P, SCR_STPS, SCR_OUT, SCR_X2, SCR_CLS, SCR_JKP, SCR_JKOUT, SCR_TAB, SCR_FZ, SCR_JKTAB, SCR_SPA, SCR_SPB, SCR_SPG, SCR_SPH, SCR_SPM, SCR_SPK, SCR_GEMM, SCR_J1TAB, SCR_J1PL, SCR_J1T, SCR_BTAB, SCR_BXG, SCR_BY, SCR_BX, SCR_BP, SCR_JBTAB, SCR_JBPL, SCR_JBT, SCR_JBY, SCR_JBX, SCR_J2TAB, SCR_J2P, SCR_J2ST, SCR_J2Y, SCR_J2X, SCR_N };
+enum { SCR_Y = 0, SCR_PART, SCR_XT, SCR_OBUF, SCR_SEL, SCR_SUBST, SCR_CONV, SCR_CHUNK, SCR_P, SCR_STPS, SCR_OUT, SCR_X2, SCR_CLS, SCR_JKP, SCR_JKOUT, SCR_TAB, SCR_FZ, SCR_JKTAB, SCR_SPA, SCR_SPB, SCR_SPG, SCR_SPH, SCR_SPM, SCR_SPK, SCR_GEMM, SCR_J1TAB, SCR_J1PL, SCR_J1T, SCR_BTAB, SCR_BXG, SCR_BY, SCR_BX, SCR_BP, SCR_JBTAB, SCR_JBPL, SCR_JBT, SCR_JBY, SCR_JBX, SCR_J2TAB, SCR_J2P, SCR_J2ST, SCR_J2Y, SCR_J2X, SCR_CBTAB, SCR_CBX, SCR_CBY, SCR_CBR, SCR_CBST, SCR_CBP, SCR_CBM, SCR_N };
 
 struct OctDesc; // inverse work items (inv_poly.h)
 struct TLItem;  // many-trace forward work items (fwd_tl.h)
@@ -277,6 +278,7 @@ struct tspws_hip_plan {
 	tspws_hip_batch_stats batch_stats{}; // how the last batched call (batch.hip) stacked its ensembles
 	tspws_hip_jk_batch_stats jk_batch_stats{}; // ... and the last batched jackknife (jk_batch.hip)
 	tspws_hip_jk_batch2_stats jk_batch2_stats{}; // ... and the last batched two-stage jackknife (jk_batch_two_stage.hip)
+	tspws_hip_conv_batch_stats conv_batch_stats{}; // ... and the last batched convergence curves (conv_batch.hip)
 };
 
 int tspws_scratch(tspws_hip_plan *p, int slot, size_t bytes, void **out);
