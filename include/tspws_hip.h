@@ -341,6 +341,52 @@ int  tspws_hip_subsample(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_
 int  tspws_hip_subsample_sel(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, size_t mtr, unsigned M,
                              const char *h_sel, float *d_ls_out, float *d_ts_out, void *stream);
 
+/* Host: the masks of a batch, sel[M][T] (1 = kept), T = first[B] - first[0]: for b = 0 .. B-1 in order, for m = 0 .. M-1 in order,
+ * tspws_subsampling_plan(the columns of ensemble b in row m, M_b, ceil(M_b * prob)) -- the rand() call order of a loop of
+ * tspws_hip_subsample over the ensembles.  Empty ensembles draw nothing.  Returns 0; 1 for NULL arguments or decreasing offsets (nothing
+ * written, nothing drawn); 2 where prob asks for more than M_b traces (prob > 1). */
+int  tspws_subsampling_plan_batch(char *sel, const size_t *first, unsigned B, unsigned M, double prob);
+/* M random subsamples of each of B ensembles of one trace array in ONE call, the masks given.  Ensemble b = the traces [h_first[b],
+ * h_first[b+1]) of d_sigall (the rules of tspws_hip_stack_batch: B + 1 non-decreasing host offsets, h_first[0] may be > 0, ld >= max);
+ * h_sel is [M][T] bytes (1 = kept; any 0/1 matrix), T = h_first[B] - h_first[0], column i - h_first[0] for trace i.  K_{b,m} = the ones of
+ * row m inside ensemble b = h_mtr_out[b][m]; with masks from tspws_subsampling_plan_batch K_{b,m} = ceil(M_b * subsmpl_p) for every m, and
+ * block [b][M][max] of d_ls_out / d_ts_out then is what tspws_hip_subsample_sel gives for ensemble b alone with its columns, to the parity
+ * tolerance (relerr 2e-6).  Every ensemble follows the single call's rule on its own size -- two-stage iff 0 < Kmax <= M_b (by M_b, not by
+ * K) -- and a batch may mix both kinds:
+ *   single-stage (tspws_subsmpl_float, :501-610): tsPWS_out = (float) Re_rec(weight(ST, PS)) of the kept traces with K = M = K_{b,m}, the
+ *     mode chosen per row (a K = 1 row takes the K = 1 rule); ls_out = the FLOAT accumulator over the kept traces in trace order (:538-542)
+ *     times (float)(1. / K_{b,m}) (:579-583);
+ *   two-stage (TwoStage_subsmpl_float, :612-709): the group of a kept trace is floor(k Kmax / K_{b,m}), k its rank among the kept traces;
+ *     weights with (Kmax, K_{b,m}); ls_out = (float)((the groups' FP64 sum) * (1 / K_{b,m})); empty groups (K_{b,m} < Kmax) count as zero rows.
+ * K_{b,m} = 0 gives zero rows and count 0 (the batch calls' choice); an empty ensemble gives zero rows and zero counts.  B == 0 or M == 0
+ * returns 0 and does nothing.  NULL plan / p / h_first / h_sel / outputs / h_mtr_out, NULL traces with T > 0, decreasing offsets and
+ * ld < max return TSPWS_E_ARG ("subsample_batch: ...") before any device work, outputs untouched; the checks that need no plan come first.
+ * Fold and mean removal stay with the caller.
+ * With ONE non-empty ensemble the call IS tspws_hip_subsample_sel for it, bit for bit, when every row has K = ceil(M_b subsmpl_p) (a
+ * two-stage ensemble: whenever no row is empty).  Otherwise, in rounds of whole ensembles: the single-stage ensembles' traces are transformed once (one
+ * forward launch sequence per stretch of contiguous traces), ONE segmented masked accumulation (coefficient tile x group of 8 masks x
+ * ensemble; the 8 mask bits of a trace in one byte) leaves every row's ST / PS planes, written once, ONE kernel forms the float-accumulator
+ * linear stacks, then the weights with each row's K, the batched inverses and the float epilogue scattered to [b][m]; the two-stage
+ * ensembles go through the shared walk of tspws_hip_jackknife_batch_two_stage without main rows.  Nothing is atomic, every sum has a fixed
+ * order: a repeated call is bit-identical.  Every scratch block that grows with the batch stays within TSPWS_PART_MB (a round never splits
+ * an ensemble; one ensemble alone may exceed it).  The call uploads its tables and waits for `stream`: on return the outputs are complete. */
+int  tspws_hip_subsample_batch_sel(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, const size_t *h_first, unsigned B,
+                                   unsigned M, const char *h_sel, float *d_ls_out, float *d_ts_out, unsigned *h_mtr_out, void *stream);
+/* The same with the masks drawn by tspws_subsampling_plan_batch(p->subsmpl_p) BEFORE the call's first device call (after its refusals: a
+ * refused call draws nothing). */
+int  tspws_hip_subsample_batch(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, const size_t *h_first, unsigned B,
+                               unsigned M, float *d_ls_out, float *d_ts_out, unsigned *h_mtr_out, void *stream);
+/* How the plan's last tspws_hip_subsample_batch[_sel] call with B > 0 and M > 0 went (all zero before the first one). */
+typedef struct {
+	unsigned single_shared;    /* single-stage ensembles that went through the segmented accumulation               */
+	unsigned two_stage_shared; /* two-stage ensembles that went through the shared walk                              */
+	unsigned looped;           /* 1: the only non-empty ensemble went through tspws_hip_subsample_sel                */
+	unsigned empty;            /* ensembles without traces (zero rows, zero counts)                                  */
+	unsigned rounds;           /* rounds of single-stage ensembles + rounds of the walk (0 when looped)              */
+	unsigned rows;             /* mask rows finished: M per non-empty ensemble                                       */
+} tspws_hip_sub_batch_stats;
+int  tspws_hip_subsample_batch_stats(const tspws_hip_plan *plan, tspws_hip_sub_batch_stats *stats);
+
 /* ---- convergence curves ------------------------------------------------------------------------ */
 /* Similarity / misfit of the stack of the first i+1 traces against a reference, for i = 0..mtr-1
  * (ts_pws1f_lib.c:247-314, similarity :433-449, misfit :452-462).  d_ref_ts / d_ref_ls are [max] floats on the

@@ -133,6 +133,10 @@ SYMBOLS = {
     "tspws_subsampling_plan": (_i, [_vp, _sz, _sz]),
     "tspws_hip_subsample": (_i, [_vp, _vp, _vp, _sz, _sz, _u, _vp, _vp, _vp]),
     "tspws_hip_subsample_sel": (_i, [_vp, _vp, _vp, _sz, _sz, _u, _vp, _vp, _vp, _vp]),
+    "tspws_subsampling_plan_batch": (_i, [_vp, _vp, _u, _u, _d]),
+    "tspws_hip_subsample_batch_sel": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _u, _vp, _vp, _vp, _vp, _vp]),
+    "tspws_hip_subsample_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _u, _vp, _vp, _vp, _vp]),
+    "tspws_hip_subsample_batch_stats": (_i, [_vp, _vp]),
     "tspws_hip_convergence": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence_batch_stats": (_i, [_vp, _vp]),
@@ -543,6 +547,70 @@ class Plan:
         check(self.lib.tspws_hip_jackknife_batch_two_stage_stats(self.h, C.byref(st)), "jackknife_batch_two_stage_stats")
         return dict(zip(("shared", "looped", "empty", "rounds", "tiles", "rows"), list(st)))
 
+    def subsample_sel(self, traces, sel, prob=None, ls_out=None, ts_out=None):
+        """The random subsamples of ONE ensemble with the masks given (tspws_hip_subsample_sel): `sel` = [M][mtr] int8 masks (1 = kept), every
+        row with K = ceil(mtr * subsmpl_p) ones (`prob` replaces the plan's subsmpl_p for this call).  Returns ls_out[M][N], ts_out[M][N]
+        (float32 cuda; given or new).  Synchronises."""
+        import numpy as np
+        import torch
+        mtr, ld = self._traces(traces)
+        if not isinstance(sel, np.ndarray) or sel.ndim != 2 or sel.dtype not in (np.int8, np.uint8, np.bool_):
+            raise TspwsError("masks must be a 2-D int8 / uint8 / bool numpy array [M][mtr]")
+        sel = self._sel(sel, sel.shape[0], mtr)
+        Mn = sel.shape[0]
+        p = t_tsPWS.from_buffer_copy(self.params)
+        if prob is not None:
+            p.subsmpl_p = prob
+        ls_out = torch.zeros((Mn, self.N), dtype=torch.float32, device=traces.device) if ls_out is None else ls_out
+        ts_out = torch.zeros((Mn, self.N), dtype=torch.float32, device=traces.device) if ts_out is None else ts_out
+        for t, name in ((ls_out, "ls_out"), (ts_out, "ts_out")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (Mn, self.N) or not t.is_contiguous() or \
+                    not t.is_cuda or (t.device.index or 0) != self.device:
+                raise TspwsError(f"{name} must be a contiguous float32 [{Mn}][{self.N}] tensor on cuda:{self.device}")
+        check(self.lib.tspws_hip_subsample_sel(self.h, C.byref(p), traces.data_ptr(), ld, mtr, Mn, sel.ctypes.data, ls_out.data_ptr(), ts_out.data_ptr(),
+                                               self._stream()), "subsample_sel")
+        return ls_out, ts_out
+
+    def subsample_batch(self, traces, first, sel, ls_out=None, ts_out=None, mtr_out=None):
+        """M random subsamples of each of B ensembles of one trace array in ONE call (tspws_hip_subsample_batch_sel): ensemble b = rows
+        [first[b], first[b+1]) of the float32 [mtr][N] device tensor `traces`; `sel` = [M][T] int8 masks (1 = kept; any 0/1 matrix),
+        T = first[B] - first[0], column i - first[0] for trace i (subsampling_selection_batch draws them).  Returns ls_out[B][M][N],
+        ts_out[B][M][N] (float32 cuda) and mtr_out[B][M] (uint32, the traces every row keeps): block b = what subsample_sel gives for ensemble b
+        alone (a row that keeps nothing and an empty ensemble: zero rows, count 0).  Synchronises."""
+        import numpy as np
+        import torch
+        mtr, ld = self._traces(traces)
+        f = np.asarray(first)
+        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
+            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
+        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
+            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
+        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
+        B, T = f.size - 1, int(f[-1] - f[0])
+        if not isinstance(sel, np.ndarray) or sel.ndim != 2 or sel.dtype not in (np.int8, np.uint8, np.bool_):
+            raise TspwsError("masks must be a 2-D int8 / uint8 / bool numpy array [M][T]")
+        sel = self._sel(sel, sel.shape[0], T)
+        Mn = sel.shape[0]
+        dev = traces.device
+        ls_out = torch.empty((B, Mn, self.N), dtype=torch.float32, device=dev) if ls_out is None else ls_out
+        ts_out = torch.empty((B, Mn, self.N), dtype=torch.float32, device=dev) if ts_out is None else ts_out
+        mtr_out = np.zeros((B, Mn), np.uint32) if mtr_out is None else mtr_out
+        if not isinstance(mtr_out, np.ndarray) or mtr_out.dtype != np.uint32 or mtr_out.shape != (B, Mn) or not mtr_out.flags.c_contiguous:
+            raise TspwsError(f"mtr_out must be a contiguous uint32 numpy array [{B}][{Mn}]")
+        for t, name in ((ls_out, "ls_out"), (ts_out, "ts_out")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (B, Mn, self.N) or not t.is_contiguous() or \
+                    not t.is_cuda or (t.device.index or 0) != self.device:
+                raise TspwsError(f"{name} must be a contiguous float32 [{B}][{Mn}][{self.N}] tensor on cuda:{self.device}")
+        check(self.lib.tspws_hip_subsample_batch_sel(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, Mn, sel.ctypes.data,
+                                                     ls_out.data_ptr(), ts_out.data_ptr(), mtr_out.ctypes.data, self._stream()), "subsample_batch_sel")
+        return ls_out, ts_out, mtr_out
+
+    def subsample_batch_stats(self):
+        """How the last subsample_batch call with B > 0 and M > 0 went (tspws_hip_subsample_batch_stats): dict of counts."""
+        st = (C.c_uint * 6)()
+        check(self.lib.tspws_hip_subsample_batch_stats(self.h, C.byref(st)), "subsample_batch_stats")
+        return dict(zip(("single_shared", "two_stage_shared", "looped", "empty", "rounds", "rows"), list(st)))
+
     def _refs(self, t, name, rows):
         """Data pointer of a reference array: contiguous float32 [rows][N] (or [N] for one row) on the plan's device."""
         import torch
@@ -847,6 +915,23 @@ def jackknife_selection_batch(times, first, n, d):
         a, e = int(f[b]), int(f[b + 1])
         if e > a:
             sel[:, a - f0:e - f0] = jackknife_selection(times[a:e], n, d)
+    return sel
+
+
+def subsampling_selection_batch(first, M, prob):
+    """Random-subsampling masks of a batch (tspws_subsampling_plan_batch): int8 [M][T], T = first[-1] - first[0]; for every ensemble in order
+    and every mask in order, ceil(M_b * prob) of the ensemble's columns of that row are 1, drawn with libc rand() in the order of a loop of
+    single calls over the ensembles."""
+    import numpy as np
+    f = np.asarray(first)
+    if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu" or (f < 0).any() or (np.diff(f) < 0).any():
+        raise TspwsError("first must be a 1-D array of B + 1 non-decreasing, non-negative integer offsets")
+    if not 0 <= prob <= 1:
+        raise TspwsError("prob must lie in [0, 1]")
+    f = np.ascontiguousarray(f, dtype=np.uint64)
+    sel = np.zeros((int(M), int(f[-1] - f[0])), np.int8)
+    if load().tspws_subsampling_plan_batch(sel.ctypes.data, f.ctypes.data, f.size - 1, int(M), float(prob)):
+        raise TspwsError("tspws_subsampling_plan_batch refused its arguments")
     return sel
 
 

@@ -303,7 +303,8 @@ void build_tile(const char *h_sel, size_t Tn, size_t col0, const Ens &e, unsigne
 }
 
 int shared_walk(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const Tables &T, unsigned C, bool main, unsigned ntile, float *d_ls,
-                float *d_ts, float *d_ls_out, float *d_ts_out, const unsigned *h_Kc, hipStream_t st, std::vector<std::vector<char>> &keep)
+                float *d_ts, float *d_ls_out, float *d_ts_out, const unsigned *h_Kc, hipStream_t st, std::vector<std::vector<char>> &keep,
+                tspws_hip_jk_batch2_stats *stats)
 {
 	const size_t N = pl->N, nc = pl->ncoef, n = T.ens.size(), budget = tspws_part_budget_bytes();
 	const unsigned KM = p->Kmax, W = C + (main ? 1u : 0u);
@@ -351,8 +352,8 @@ int shared_walk(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t l
 	for (const Round &r : rounds) {
 		const size_t ne = r.j1 - r.j0, nrep = ne * C, nsl = ne * W, nsets = nrep + (main ? 2 * ne : 0), nrows = nsl * KM;
 		const size_t q0 = T.run_ptr[r.j0 * ntile], nruns = T.run_ptr[r.j1 * ntile] - q0, f0 = T.flush_ptr[r.j0], nfl = T.flush_ptr[r.j1] - f0;
-		pl->jk_batch2_stats.rounds++;
-		pl->jk_batch2_stats.rows += (unsigned)nrows;
+		stats->rounds++;
+		stats->rows += (unsigned)nrows;
 		// the round's tables in one block: trace counts (doubles) | runs | (ensemble, tile) run ranges | flush rows | counts | output rows
 		const size_t o_run = nsl * sizeof(double), o_wg = o_run + nruns * sizeof(RunDesc), o_fl = o_wg + ne * ntile * sizeof(J2Wg), o_cnt = o_fl + nfl * 4,
 		             o_row = o_cnt + nsl * 4, bytes = o_row + nsl * 4;
@@ -416,6 +417,34 @@ int shared_walk(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t l
 
 } // namespace
 
+// The shared walk over the ensembles list[0 .. n) of a batch (indices into h_first, ascending; every one two-stage, with traces; column
+// h_first[b] - h_first[0] of h_sel[C][Tn] is the first of ensemble b): host tables in one pass over the selection, then rounds of whole ensembles.
+// Ensemble b writes rows b * C + c of the replica outputs and of h_mtr_out and, with `main`, row b of d_ls / d_ts; stats: rounds and rows are
+// counted up.  `keep` holds the host sources of the uploads: the caller synchronises `st` before it lets them go.  (Also what
+// tspws_hip_subsample_batch runs for its two-stage ensembles, sub_batch.hip.)
+int tspws_jb2_shared(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *h_first, const unsigned *list, size_t n, const char *h_sel,
+                     size_t Tn, unsigned C, bool main, float *d_ls, float *d_ts, float *d_ls_out, float *d_ts_out, unsigned *h_mtr_out, hipStream_t st,
+                     std::vector<std::vector<char>> &keep, tspws_hip_jk_batch2_stats *stats)
+{
+	const unsigned KM = p->Kmax, W = C + (main ? 1u : 0u), ntile = (W + J2_W - 1) / J2_W;
+	Tables T;
+	T.run_ptr.push_back(0);
+	T.flush_ptr.push_back(0);
+	for (size_t k = 0; k < n; k++) {
+		const unsigned b = list[k];
+		Ens e;
+		e.b = b; e.f = h_first[b]; e.m = h_first[b + 1] - e.f; e.unwritten = false;
+		for (unsigned q = 0; q < ntile; q++) {
+			build_tile(h_sel, Tn, e.f - h_first[0], e, KM, C, q * J2_W, std::min(W, (q + 1) * J2_W), h_mtr_out + (size_t)b * C, T, e.unwritten);
+			T.run_ptr.push_back(T.runs.size());
+		}
+		T.flush_ptr.push_back(T.flush.size());
+		T.ens.push_back(e);
+		if (T.flush.size() > 0xfffffff0ull) return fail(TSPWS_E_ARG, "jackknife_batch_two_stage: more than 2^32 partial-stack rows");
+	}
+	return shared_walk(pl, p, d_x, ld, T, C, main, ntile, d_ls, d_ts, d_ls_out, d_ts_out, h_mtr_out, st, keep, stats);
+}
+
 extern "C" int tspws_hip_jackknife_batch_two_stage(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *h_first, unsigned B,
                                                    const char *h_sel, unsigned C, float *d_ls, float *d_ts, float *d_ls_out, float *d_ts_out,
                                                    unsigned *h_mtr_out, void *s)
@@ -462,23 +491,9 @@ extern "C" int tspws_hip_jackknife_batch_two_stage(tspws_hip_plan *pl, const t_t
 		if (rc) return rc;
 		HIP_TRY(hipStreamSynchronize(st)); // (`sel` goes out of scope)
 	} else if (nonempty.size() > 1) {
-		// host tables of the whole batch in one pass over the selection
-		Tables T;
-		T.run_ptr.push_back(0);
-		T.flush_ptr.push_back(0);
-		for (unsigned b : nonempty) {
-			Ens e;
-			e.b = b; e.f = h_first[b]; e.m = h_first[b + 1] - e.f; e.unwritten = false;
-			for (unsigned q = 0; q < ntile; q++) {
-				build_tile(h_sel, Tn, e.f - h_first[0], e, KM, C, q * J2_W, std::min(W, (q + 1) * J2_W), h_mtr_out + (size_t)b * C, T, e.unwritten);
-				T.run_ptr.push_back(T.runs.size());
-			}
-			T.flush_ptr.push_back(T.flush.size());
-			T.ens.push_back(e);
-			if (T.flush.size() > 0xfffffff0ull) return fail(TSPWS_E_ARG, "jackknife_batch_two_stage: more than 2^32 partial-stack rows");
-		}
-		pl->jk_batch2_stats.shared = (unsigned)T.ens.size();
-		if ((rc = shared_walk(pl, p, d_x, ld, T, C, main, ntile, d_ls, d_ts, d_ls_out, d_ts_out, h_mtr_out, st, keep))) { (void)hipStreamSynchronize(st); return rc; }
+		pl->jk_batch2_stats.shared = (unsigned)nonempty.size();
+		if ((rc = tspws_jb2_shared(pl, p, d_x, ld, h_first, nonempty.data(), nonempty.size(), h_sel, Tn, C, main, d_ls, d_ts, d_ls_out, d_ts_out, h_mtr_out, st, keep,
+		                           &pl->jk_batch2_stats))) { (void)hipStreamSynchronize(st); return rc; }
 	}
 	// empty ensembles: zero rows, zero counts
 	for (unsigned b = 0; b < B; b++)

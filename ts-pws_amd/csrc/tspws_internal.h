@@ -14,6 +14,7 @@
 //   jk_batch.hip  single-stage jackknife of many ensembles in one call (batch_kernels.h: the small kernels those three share)
 //   jk_batch_two_stage.hip  two-stage jackknife of many ensembles in one call
 //   conv_batch.hip  convergence curves of many ensembles in one call
+//   sub_batch.hip   random subsamples of many ensembles in one call
 //   comm.hip      trace shards on several devices of one process: RCCL all-reduce, sharded tspws_main driver
 //
 // Layout in HBM
@@ -177,7 +178,7 @@ struct AccExtra {
 	bool fused_done = false;          // the fused forward kernel completed (and weighted) the stacks of its scales itself: only the others are left
 };
 
-enum { SCR_Y = 0, SCR_PART, SCR_XT, SCR_OBUF, SCR_SEL, SCR_SUBST, SCR_CONV, SCR_CHUNK, SCR_P, SCR_STPS, SCR_OUT, SCR_X2, SCR_CLS, SCR_JKP, SCR_JKOUT, SCR_TAB, SCR_FZ, SCR_JKTAB, SCR_SPA, SCR_SPB, SCR_SPG, SCR_SPH, SCR_SPM, SCR_SPK, SCR_GEMM, SCR_J1TAB, SCR_J1PL, SCR_J1T, SCR_BTAB, SCR_BXG, SCR_BY, SCR_BX, SCR_BP, SCR_JBTAB, SCR_JBPL, SCR_JBT, SCR_JBY, SCR_JBX, SCR_J2TAB, SCR_J2P, SCR_J2ST, SCR_J2Y, SCR_J2X, SCR_CBTAB, SCR_CBX, SCR_CBY, SCR_CBR, SCR_CBST, SCR_CBP, SCR_CBM, SCR_N };
+enum { SCR_Y = 0, SCR_PART, SCR_XT, SCR_OBUF, SCR_SEL, SCR_SUBST, SCR_CONV, SCR_CHUNK, SCR_P, SCR_STPS, SCR_OUT, SCR_X2, SCR_CLS, SCR_JKP, SCR_JKOUT, SCR_TAB, SCR_FZ, SCR_JKTAB, SCR_SPA, SCR_SPB, SCR_SPG, SCR_SPH, SCR_SPM, SCR_SPK, SCR_GEMM, SCR_J1TAB, SCR_J1PL, SCR_J1T, SCR_BTAB, SCR_BXG, SCR_BY, SCR_BX, SCR_BP, SCR_JBTAB, SCR_JBPL, SCR_JBT, SCR_JBY, SCR_JBX, SCR_J2TAB, SCR_J2P, SCR_J2ST, SCR_J2Y, SCR_J2X, SCR_CBTAB, SCR_CBX, SCR_CBY, SCR_CBR, SCR_CBST, SCR_CBP, SCR_CBM, SCR_SBTAB, SCR_SBPL, SCR_SBY, SCR_SBX, SCR_N };
 
 struct OctDesc; // inverse work items (inv_poly.h)
 struct TLItem;  // many-trace forward work items (fwd_tl.h)
@@ -279,6 +280,7 @@ struct tspws_hip_plan {
 	tspws_hip_jk_batch_stats jk_batch_stats{}; // ... and the last batched jackknife (jk_batch.hip)
 	tspws_hip_jk_batch2_stats jk_batch2_stats{}; // ... and the last batched two-stage jackknife (jk_batch_two_stage.hip)
 	tspws_hip_conv_batch_stats conv_batch_stats{}; // ... and the last batched convergence curves (conv_batch.hip)
+	tspws_hip_sub_batch_stats sub_batch_stats{}; // ... and the last batched random subsampling (sub_batch.hip)
 };
 
 int tspws_scratch(tspws_hip_plan *p, int slot, size_t bytes, void **out);
@@ -440,5 +442,9 @@ int  tspws_rows_walk_launch(const float *d_x, size_t ld, size_t N, const RunDesc
                             const unsigned *d_flush_rows, const unsigned *d_fix_row, double *d_rows, double *d_blk, int carry_in, int carry_out, hipStream_t st);
 unsigned tspws_rows_walk_wmax();
 unsigned tspws_chunk_len_for(size_t N, size_t mtr);
+// jk_batch_two_stage.hip: the shared walk over the two-stage ensembles list[0 .. n) of a batch (see there)
+int  tspws_jb2_shared(tspws_hip_plan *p, const t_tsPWS *par, const float *d_x, size_t ld, const size_t *h_first, const unsigned *list, size_t n,
+                      const char *h_sel, size_t Tn, unsigned C, bool main, float *d_ls, float *d_ts, float *d_ls_out, float *d_ts_out, unsigned *h_mtr_out,
+                      hipStream_t st, std::vector<std::vector<char>> &keep, tspws_hip_jk_batch2_stats *stats);
 // stack.hip
 bool tspws_is_two_stage(const t_tsPWS *p, size_t mtr_global);
