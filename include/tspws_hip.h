@@ -121,6 +121,19 @@ int  tspws_hip_forward_spectral_f32(tspws_hip_plan *plan, const float  *d_x, siz
  * d_x[nrec][N] doubles.  Takes over Re_complex_1D_wavelet_rec (wavelet_v7.c:124-150) ->
  * re_cdotx_upsampling_cc (cdotx.c:305-340) / re_cdotx_cc (cdotx.c:176-211). */
 int  tspws_hip_inverse(tspws_hip_plan *plan, const double *d_Y, size_t nrec, double *d_x, void *stream);
+/* How tspws_hip_inverse launches this plan's frame (read-only, no device work): the work list of the polyphase kernel k_inv_poly and the
+ * wave ranges of its instantiations, so that a test can assert the route it means to take.  Waves [0, waves_lds) take the LDS-staged
+ * instantiation when a call has two or more pairs of sets (the per-lane one otherwise), [waves_lds, waves_fast) the per-lane / wave-uniform
+ * one, [waves_fast, waves) the three-frame GEN one (decimations that do not divide N). */
+typedef struct {
+	unsigned items;      /* work items of the launch list                                                        */
+	unsigned per_scale;  /* 1: one item per scale (the short-frame form), 0: one per decimation octave           */
+	unsigned waves;      /* waves of the whole list                                                              */
+	unsigned waves_lds;  /* ... of which the first waves_lds are LDS-staged in calls with two or more pairs       */
+	unsigned waves_fast; /* waves of the items whose D divides N (the GEN waves are waves - waves_fast)            */
+	unsigned generic;    /* 1: k_inverse_generic is in force instead (TSPWS_INV_GENERIC=1 of the sweeps build)     */
+} tspws_hip_inverse_info_t;
+int  tspws_hip_inverse_info(const tspws_hip_plan *plan, tspws_hip_inverse_info_t *info);
 
 /* ---- stacks in the time-scale domain ----------------------------------------------- */
 /* ST += sum_b Y_b ; PS += sum_b Y_b/|Y_b| (non-unit quotients skipped); zero_first clears

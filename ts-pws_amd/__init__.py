@@ -49,6 +49,12 @@ class FrameInfo(C.Structure):
     ]
 
 
+class InverseInfo(C.Structure):
+    """tspws_hip_inverse_info_t (include/tspws_hip.h)."""
+    _fields_ = [("items", C.c_uint), ("per_scale", C.c_uint), ("waves", C.c_uint), ("waves_lds", C.c_uint), ("waves_fast", C.c_uint),
+                ("generic", C.c_uint)]
+
+
 class TspwsError(RuntimeError):
     pass
 
@@ -96,6 +102,7 @@ SYMBOLS = {
     "tspws_hip_forward_spectral_f64": (_i, [_vp, _vp, _sz, _sz, _vp, _u, _vp]),
     "tspws_hip_forward_spectral_f32": (_i, [_vp, _vp, _sz, _sz, _vp, _u, _vp]),
     "tspws_hip_inverse": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "tspws_hip_inverse_info": (_i, [_vp, _vp]),
     "tspws_hip_accumulate": (_i, [_vp, _vp, _sz, _vp, _vp, _i, _vp]),
     "tspws_hip_stacks_double": (_i, [_vp, _vp, _u, _sz, _vp, _vp, _vp]),
     "tspws_hip_stacks_float": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
@@ -290,6 +297,35 @@ class Plan:
         check(fn(self.h, traces.data_ptr(), mtr, ld, ST.data_ptr(), PS.data_ptr(), self._stream()), "stacks")
         torch.cuda.synchronize(traces.device)
         return ST.cpu().numpy().view(np.complex128), PS.cpu().numpy().view(np.complex128)
+
+    def inverse_info(self):
+        """How tspws_hip_inverse launches this frame (tspws_hip_inverse_info): dict(items, per_scale, waves, waves_lds, waves_fast, generic)."""
+        info = InverseInfo()
+        check(self.lib.tspws_hip_inverse_info(self.h, C.byref(info)), "inverse_info")
+        return {k: int(getattr(info, k)) for k, _ in InverseInfo._fields_}
+
+    def inverse(self, Y):
+        """Real part of the inverse frame transform of the coefficient sets Y[nrec][ncoef] in ONE tspws_hip_inverse call: a complex128 numpy
+        array (returns float64 numpy [nrec][N]) or a contiguous complex128 tensor on the plan's device (returns a float64 tensor there).
+        The output holds NaN before the call (an unwritten sample shows); synchronises."""
+        import numpy as np
+        import torch
+        if isinstance(Y, np.ndarray):
+            if Y.dtype != np.complex128 or Y.ndim != 2 or Y.shape[1] != self.ncoef or not Y.shape[0]:
+                raise TspwsError(f"Y must be complex128 [nrec >= 1][{self.ncoef}], got {Y.dtype} {Y.shape}")
+            Yd = torch.as_tensor(np.ascontiguousarray(Y), device=f"cuda:{self.device}")
+        elif isinstance(Y, torch.Tensor):
+            if Y.dtype != torch.complex128 or Y.dim() != 2 or Y.shape[1] != self.ncoef or not Y.shape[0]:
+                raise TspwsError(f"Y must be complex128 [nrec >= 1][{self.ncoef}], got {Y.dtype} {tuple(Y.shape)}")
+            if not Y.is_cuda or (Y.device.index or 0) != self.device or not Y.is_contiguous():
+                raise TspwsError(f"Y must be a contiguous tensor on cuda:{self.device}, got {Y.device}")
+            Yd = Y
+        else:
+            raise TspwsError("Y must be a complex128 numpy array or device tensor")
+        x = torch.full((Yd.shape[0], self.N), float("nan"), dtype=torch.float64, device=Yd.device)
+        check(self.lib.tspws_hip_inverse(self.h, Yd.data_ptr(), Yd.shape[0], x.data_ptr(), self._stream()), "inverse")
+        torch.cuda.synchronize(Yd.device)
+        return x.cpu().numpy() if isinstance(Y, np.ndarray) else x
 
     def stack_local(self, traces, first=0, mtr_global=None):
         mtr, ld = self._traces(traces)

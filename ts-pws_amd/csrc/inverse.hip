@@ -298,6 +298,16 @@ extern "C" int tspws_hip_inverse(tspws_hip_plan *p, const double *d_Y, size_t nr
 	return 0;
 }
 
+extern "C" int tspws_hip_inverse_info(const tspws_hip_plan *p, tspws_hip_inverse_info_t *info)
+{
+	if (!p || !info) return fail(TSPWS_E_ARG, "inverse_info: NULL");
+	info->items = p->inv_noct;
+	info->per_scale = p->inv_noct == p->S ? 1u : 0u;
+	info->waves = p->inv_waves; info->waves_lds = p->inv_waves_lds; info->waves_fast = p->inv_waves_fast;
+	info->generic = (tspws_generic_inverse() || p->inv_noct == 0) ? 1u : 0u;
+	return 0;
+}
+
 // Batched pairs of reconstructions in TWO halves (the one-pass stack + jackknife call, resample.hip): the octaves of the scales [0, s_split) --
 // those the FIR forward kernels completed -- EARLY, on the stream `early` on which their weighted coefficient sets are complete, beside whatever
 // the caller's stream still runs (the spectral chain of the other scales: its tail is a run of short, latency-bound kernels); the other octaves
