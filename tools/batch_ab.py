@@ -1,0 +1,157 @@
+#!/usr/bin/env python3
+"""Bit-for-bit comparison of the batched entry points between two builds of the library: the parent's (ts-pws_amd/lib/variant_base.so, from
+tools/build_base.sh) and the working tree's.  For each library and for TSPWS_PART_MB unset and = 16 a fresh child process (library by
+TSPWS_LIB_PATH) runs the seven entry points -- stack_batch, jackknife_single, jackknife_batch, jackknife_batch_two_stage, convergence_batch,
+subsample_batch_sel (masks given) and subsample_batch (masks drawn after srand) -- on seeded inputs and stores every float output and count; the parent process compares the stored arrays
+byte for byte and exits non-zero on any difference.
+
+Shapes: 13 ensembles of 0-70 traces (one empty, one of 70 that straddles a 64-trace block, one of exactly 64), N = 4096 and N = 4001; the
+single-stage parameter set and Kmax = 10, unbiased; 9 jackknife columns for the single-stage jackknives, 17 columns / masks (two column tiles
+of the two-stage walk, three mask groups) for the others.  A child fails unless the stats calls say that the shared paths ran.
+usage: batch_ab.py [base.so new.so]      (child: batch_ab.py run out.npz)"""
+import ctypes as C
+import importlib
+import os
+import subprocess
+import sys
+import tempfile
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.join(HERE, "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+
+SIZES_MIXED = [1, 5, 33, 70, 0, 12, 64, 40, 17, 65, 28, 9, 30]   # single-stage under either parameter set: 1, 5, 9
+SIZES_TWO = [10, 15, 33, 70, 0, 12, 64, 40, 17, 65, 28, 11, 30]  # every non-empty ensemble two-stage with Kmax = 10
+NS = (4096, 4001)
+C1, C2 = 9, 17
+
+
+def bins_selection(sizes, C):
+    """[C][T] delete-one selection: trace i of an ensemble sits in bin i % C, column c drops bin c (ensembles shorter than C: empty bins)."""
+    sel = np.ones((C, sum(sizes)), np.int8)
+    t = 0
+    for m in sizes:
+        for i in range(m):
+            sel[i % C, t + i] = 0
+        t += m
+    return sel
+
+
+def child(path):
+    import torch
+    import abi
+    tspws = importlib.import_module("ts-pws_amd")
+    out = {}
+
+    def keep(tag, *arrays):
+        for k, a in enumerate(arrays):
+            out[f"{tag}.{k}"] = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+    for N in NS:
+        pl = tspws.Plan(tspws.resolve(abi.default_params(), N), N)
+
+        def params(two):
+            pl.params.Kmax, pl.params.unbiased = (10, 1) if two else (0, 0)
+
+        first_m = np.concatenate([[0], np.cumsum(SIZES_MIXED)]).astype(np.int64) + 2
+        first_t = np.concatenate([[0], np.cumsum(SIZES_TWO)]).astype(np.int64) + 2
+        X = tspws.synth(int(max(first_m[-1], first_t[-1])), N, seed=N)
+        masks = (np.random.default_rng(N).random((C2, sum(SIZES_MIXED))) < 0.6).astype(np.int8)
+        for two in (False, True):
+            params(two)
+            tag = f"N{N}.{'two' if two else 'one'}"
+            n2 = sum(1 for m in SIZES_MIXED if two and m >= 10)
+            n1 = sum(1 for m in SIZES_MIXED if m) - n2
+            # stack_batch: mixed sizes
+            keep(tag + ".stack", *pl.stack_batch(X, first_m))
+            st = pl.batch_stats()
+            # (the three single-stage ensembles of the two-stage set are too few traces for the many-trace pass: looped)
+            assert st["two_stage_pass"] == n2 and st["empty"] == 1 and ((st["single_pass"], st["looped"]) == ((0, n1) if two else (n1, 0))), st
+            # convergence_batch against the ensembles' own stacks, with the steps
+            keep(tag + ".conv", *pl.convergence_batch(X, first_m, steps=True))
+            st = pl.convergence_batch_stats()
+            assert st["looped"] == 0 and st["single_steps"] > 0 and (st["two_stage_steps"] > 0) == two and st["rounds"] >= 1, st
+            # subsample_batch with the masks given
+            keep(tag + ".sub", *pl.subsample_batch(X, first_m, masks))
+            st = pl.subsample_batch_stats()
+            assert st["single_shared"] == n1 and st["two_stage_shared"] == n2 and st["looped"] == 0 and st["empty"] == 1, st
+            # ... and with the masks drawn by the call itself, from a seeded rand()
+            B = len(SIZES_MIXED)
+            sl = torch.full((B, C2, N), float("nan"), dtype=torch.float32, device="cuda")
+            st2 = torch.full((B, C2, N), float("nan"), dtype=torch.float32, device="cuda")
+            sm = np.full((B, C2), 99, np.uint32)
+            f = np.ascontiguousarray(first_m, dtype=np.uint64)
+            pl.params.subsmpl_p = 0.6
+            abi.srand(N + two)
+            rc = pl.lib.tspws_hip_subsample_batch(pl.h, C.byref(pl.params), X.data_ptr(), X.stride(0), f.ctypes.data, B, C2, sl.data_ptr(), st2.data_ptr(),
+                                                  sm.ctypes.data, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            assert rc == 0, pl.lib.tspws_hip_last_error()
+            keep(tag + ".sub_drawn", sl, st2, sm)
+            st = pl.subsample_batch_stats()
+            assert st["single_shared"] == n1 and st["two_stage_shared"] == n2 and st["looped"] == 0, st
+            if not two:
+                sel = bins_selection(SIZES_MIXED, C1)
+                keep(tag + ".jkb", *pl.jackknife_batch(X, first_m, sel))
+                st = pl.jackknife_batch_stats()
+                assert st["shared"] == 12 and st["looped"] == 0 and st["empty"] == 1 and st["rounds"] >= 1, st
+                keep(tag + ".jkb_nomain", *pl.jackknife_batch(X, first_m, sel, main=False)[2:])
+                f0, f1 = int(first_m[3]), int(first_m[4])  # the ensemble of 70 traces alone
+                keep(tag + ".jk1", *pl.jackknife_single(X[f0:f1], np.ascontiguousarray(sel[:, f0 - 2:f1 - 2])))
+                keep(tag + ".jk1_many_classes", *pl.jackknife_single(X[f0:f1], np.ascontiguousarray(masks[:C1, f0 - 2:f1 - 2])))  # > 24 classes: no LDS
+            else:
+                sel = bins_selection(SIZES_TWO, C2)
+                keep(tag + ".jkb2", *pl.jackknife_batch_two_stage(X, first_t, sel))
+                st = pl.jackknife_batch_two_stage_stats()
+                assert st["shared"] == 12 and st["looped"] == 0 and st["empty"] == 1 and st["tiles"] == 2 and st["rounds"] >= 1, st
+                keep(tag + ".jkb2_nomain", *pl.jackknife_batch_two_stage(X, first_t, sel, main=False)[2:])
+        pl.close()
+    torch.cuda.synchronize()
+    np.savez(path, **out)
+    print("AB_DONE", len(out), "arrays")
+
+
+def main():
+    libdir = os.path.join(ROOT, "ts-pws_amd", "lib")
+    libs = sys.argv[1:3] if len(sys.argv) >= 3 else [os.path.join(libdir, "variant_base.so"), os.path.join(libdir, "libtspws_hip.so")]
+    bad = 0
+    with tempfile.TemporaryDirectory() as tmp:
+        for budget in (None, "16"):
+            res = []
+            for k, lib in enumerate(libs):
+                env = dict(os.environ, TSPWS_LIB_PATH=os.path.abspath(lib))
+                env.pop("TSPWS_PART_MB", None)
+                if budget:
+                    env["TSPWS_PART_MB"] = budget
+                path = os.path.join(tmp, f"{k}_{budget}.npz")
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "run", path], env=env, capture_output=True, text=True, timeout=600)
+                if r.returncode or "AB_DONE" not in r.stdout:
+                    print(r.stdout[-3000:], r.stderr[-3000:])
+                    sys.exit(f"child failed: {lib} TSPWS_PART_MB={budget}")
+                res.append(np.load(path))
+            a, b = res
+            assert sorted(a.files) == sorted(b.files)
+            nbytes = diff = 0
+            for key in sorted(a.files):
+                x, y = a[key], b[key]
+                assert x.dtype == y.dtype and x.shape == y.shape, key
+                d = int((np.frombuffer(x.tobytes(), np.uint8) != np.frombuffer(y.tobytes(), np.uint8)).sum())
+                nbytes += x.nbytes
+                diff += d
+                if d:
+                    print(f"  DIFF {key}: {d} of {x.nbytes} bytes")
+                if x.dtype.kind == "f" and x.size and not np.isfinite(x).all():
+                    print(f"  (not finite in both: {key})")
+            print(f"TSPWS_PART_MB={budget or 'unset'}: {len(a.files)} arrays, {nbytes} bytes compared, {diff} differing bytes")
+            bad += diff
+    print("shapes: ensembles", SIZES_MIXED, "(mixed) /", SIZES_TWO, "(two-stage), first[0] = 2, N in", NS, f"C = {C1} / {C2}, M = {C2}")
+    print("libraries:", *[os.path.basename(p) for p in libs])
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    if len(sys.argv) > 2 and sys.argv[1] == "run":
+        child(sys.argv[2])
+    else:
+        main()

@@ -21,6 +21,7 @@
 // tspws_hip_stack per ensemble.  tspws_hip_stack_batch_stats tells which way the last call's ensembles went.
 #include "tspws_internal.h"
 #include "batch_kernels.h"
+#include "batch_host.h"
 
 #define is_two_stage tspws_is_two_stage
 
@@ -39,10 +40,9 @@ __global__ void __launch_bounds__(256) k_batch_epilogue(const double *__restrict
 
 namespace {
 
-// host sources of a call's uploads: alive until its final synchronisation (a copy from pageable memory may still read them after
-// hipMemcpyAsync has returned)
+// the chunk tables of the two-stage rounds: sources of tspws_run_chunks' uploads like the blocks of the BatchCall, but typed vectors of the
+// caller's -- the entry point declares them BEFORE its BatchCall, so that they are destroyed after its destructor has waited for the stream
 struct HostTables {
-	std::vector<char> blob;
 	std::vector<std::vector<Chunk>> chunks;
 	std::vector<std::vector<unsigned>> row_first;
 };
@@ -62,13 +62,11 @@ int round_bufs(tspws_hip_plan *pl, size_t nr, RoundBufs *b)
 	return 0;
 }
 
-// stacks per round: every per-stack scratch block within the parts budget -- the sets (SCR_BY), the reconstructions (SCR_BX), the inverse's
-// octave buffer (SCR_OBUF: a 2 N slot per octave item, + 1 for the generic scales) and `extra` bytes per stack of the caller's own --, at
-// most 65535 (grid.y)
+// stacks per round: every per-stack scratch block within the parts budget -- the sets (SCR_BY: OUT, ST, PS and an unused one), the two rows of
+// the inverse (its sets, reconstructions and octave buffer) and `extra` bytes per stack of the caller's own --, at most 65535 (grid.y)
 size_t round_size(const tspws_hip_plan *pl, size_t n, size_t extra)
 {
-	const size_t sets = 4 * pl->ncoef * sizeof(double2), x = 2 * (size_t)pl->N * sizeof(double), obuf = (size_t)(pl->inv_noct + 1) * x;
-	const size_t r = tspws_part_budget_bytes() / std::max({sets, x, obuf, extra});
+	const size_t r = tspws_part_budget_bytes() / std::max({4 * pl->ncoef * sizeof(double2), 2 * tspws_inverse_row_bytes(pl), extra});
 	return std::max<size_t>(1, std::min<size_t>({r, n, 65535}));
 }
 
@@ -83,30 +81,29 @@ int round_finish(tspws_hip_plan *pl, const RoundBufs &b, unsigned nr, const unsi
 
 // Single-stage ensembles `ens` (all with traces) through one many-trace pass.
 int batch_single(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *first, const std::vector<unsigned> &ens,
-                 size_t total, float *d_ls, float *d_ts, hipStream_t st, HostTables &keep)
+                 size_t total, float *d_ls, float *d_ts, BatchCall &call)
 {
 	const size_t N = pl->N, nc = pl->ncoef, n = ens.size();
+	hipStream_t st = call.stream();
 	int rc;
 	void *v;
-	std::vector<char> &keep_alive = keep.blob;
 	// block layout of every ensemble (the whole call), the gather table of its slots, output rows and trace counts
 	std::vector<size_t> blk0(n + 1);
 	for (size_t j = 0; j < n; j++) blk0[j + 1] = blk0[j] + (first[ens[j] + 1] - first[ens[j]] + 63) / 64;
 	const size_t nslots = blk0[n] * 64;
-	const size_t o_row = nslots * sizeof(long long), o_cnt = o_row + n * sizeof(unsigned), bytes = o_cnt + n * sizeof(unsigned);
-	keep_alive.assign(bytes, 0);
-	long long *src = (long long *)keep_alive.data();
-	unsigned *row = (unsigned *)(keep_alive.data() + o_row), *cnt = (unsigned *)(keep_alive.data() + o_cnt);
+	TableLayout lay;
+	const size_t o_src = lay.add<long long>(nslots), o_row = lay.add<unsigned>(n), o_cnt = lay.add<unsigned>(n);
+	char *blob = call.block(lay.bytes), *tab;
+	long long *src = (long long *)(blob + o_src);
+	unsigned *row = (unsigned *)(blob + o_row), *cnt = (unsigned *)(blob + o_cnt);
 	for (size_t j = 0; j < n; j++) {
 		const size_t f = first[ens[j]], m = first[ens[j] + 1] - f;
 		for (size_t i = 0; i < (blk0[j + 1] - blk0[j]) * 64; i++) src[blk0[j] * 64 + i] = i < m ? (long long)(f + i) : -1;
 		row[j] = ens[j];
 		cnt[j] = (unsigned)m;
 	}
-	if ((rc = scratch(pl, SCR_BTAB, bytes, &v))) return rc;
-	char *tab = (char *)v;
-	HIP_TRY(hipMemcpyAsync(tab, keep_alive.data(), bytes, hipMemcpyHostToDevice, st));
-	const long long *d_src = (const long long *)tab;
+	if ((rc = call.upload(pl, SCR_BTAB, blob, lay.bytes, &tab))) return rc;
+	const long long *d_src = (const long long *)(tab + o_src);
 	const unsigned *d_row = (const unsigned *)(tab + o_row), *d_cnt = (const unsigned *)(tab + o_cnt);
 
 	TlPass P;
@@ -167,25 +164,25 @@ int batch_single(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t 
 
 // Two-stage ensembles `ens` (Kmax <= M_b): one streaming pass for all their partial-stack rows, the rows through the few-trace forward.
 int batch_two_stage(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *first, const std::vector<unsigned> &ens,
-                    size_t total, float *d_ls, float *d_ts, hipStream_t st, HostTables &keep)
+                    size_t total, float *d_ls, float *d_ts, BatchCall &call, HostTables &chunk_tabs)
 {
 	const size_t N = pl->N, nc = pl->ncoef, n = ens.size();
 	const unsigned K = p->Kmax;
+	hipStream_t st = call.stream();
 	int rc;
 	void *v;
-	const size_t o_cnt = n * sizeof(unsigned), o_mv = (o_cnt + n * sizeof(unsigned) + 7) & ~(size_t)7, bytes = o_mv + n * sizeof(double);
-	keep.blob.assign(bytes, 0);
-	unsigned *row = (unsigned *)keep.blob.data(), *cnt = (unsigned *)(keep.blob.data() + o_cnt);
-	double *Mv = (double *)(keep.blob.data() + o_mv);
+	TableLayout lay;
+	const size_t o_row = lay.add<unsigned>(n), o_cnt = lay.add<unsigned>(n), o_mv = lay.add<double>(n);
+	char *blob = call.block(lay.bytes), *tab;
+	unsigned *row = (unsigned *)(blob + o_row), *cnt = (unsigned *)(blob + o_cnt);
+	double *Mv = (double *)(blob + o_mv);
 	for (size_t j = 0; j < n; j++) {
 		row[j] = ens[j];
 		cnt[j] = (unsigned)(first[ens[j] + 1] - first[ens[j]]);
 		Mv[j] = (double)cnt[j];
 	}
-	if ((rc = scratch(pl, SCR_BTAB, bytes, &v))) return rc;
-	char *tab = (char *)v;
-	HIP_TRY(hipMemcpyAsync(tab, keep.blob.data(), bytes, hipMemcpyHostToDevice, st));
-	const unsigned *d_row = (const unsigned *)tab, *d_cnt = (const unsigned *)(tab + o_cnt);
+	if ((rc = call.upload(pl, SCR_BTAB, blob, lay.bytes, &tab))) return rc;
+	const unsigned *d_row = (const unsigned *)(tab + o_row), *d_cnt = (const unsigned *)(tab + o_cnt);
 	const double *d_Mv = (const double *)(tab + o_mv);
 
 	// every ensemble's streaming work items: group g = floor(i Kmax / M_b) of its traces (ts_pws1f_lib.c:876), cut into equal pieces
@@ -220,16 +217,14 @@ int batch_two_stage(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size
 	double *rows = (double *)v;
 	if ((rc = scratch(pl, SCR_PART, R * K * pl->npart * sizeof(double2), &v))) return rc;
 	double2 *part = (double2 *)v;
-	for (size_t r0 = 0, r1; r0 < n; r0 = r1) {
-		r1 = r0 + 1;
-		while (r1 < n && r1 - r0 < R && ck0[r1 + 1] - ck0[r0] <= ck_cap) r1++;
-		const size_t nr = r1 - r0;
+	for (const Round &rd : whole_ensemble_rounds(n, [&](size_t j0, size_t j1) { return j1 - j0 <= R && ck0[j1] - ck0[j0] <= ck_cap; })) {
+		const size_t r0 = rd.j0, r1 = rd.j1, nr = r1 - r0;
 		pl->batch_stats.rounds++;
 		// chunk table of the round: row jr * K + g = group g of stack jr
-		keep.chunks.emplace_back(all.begin() + ck0[r0], all.begin() + ck0[r1]);
-		keep.row_first.emplace_back(nr * K + 1, 0);
-		std::vector<Chunk> &ck = keep.chunks.back();
-		std::vector<unsigned> &rf = keep.row_first.back();
+		chunk_tabs.chunks.emplace_back(all.begin() + ck0[r0], all.begin() + ck0[r1]);
+		chunk_tabs.row_first.emplace_back(nr * K + 1, 0);
+		std::vector<Chunk> &ck = chunk_tabs.chunks.back();
+		std::vector<unsigned> &rf = chunk_tabs.row_first.back();
 		for (size_t jr = 0; jr < nr; jr++)
 			for (size_t q = ck0[r0 + jr] - ck0[r0]; q < ck0[r0 + jr + 1] - ck0[r0]; q++) ck[q].row += (unsigned)(jr * K);
 		for (size_t q = ck.size(); q-- > 0;) rf[ck[q].row] = (unsigned)q; // (every group has traces: Kmax <= M_b)
@@ -270,33 +265,27 @@ extern "C" int tspws_hip_stack_batch(tspws_hip_plan *pl, const t_tsPWS *p, const
 		if (is_two_stage(p, m)) { two.push_back(b); n2 += m; }
 		else { one.push_back(b); n1 += m; }
 	}
-	HostTables tab1, tab2;
+	HostTables chunk_tabs; // (before `call`: see HostTables)
+	BatchCall call(st);
 	pl->batch_stats = tspws_hip_batch_stats();
 	pl->batch_stats.empty = B - (unsigned)(one.size() + two.size());
+	auto looped = [&](const std::vector<unsigned> &list) { // one tspws_hip_stack per ensemble
+		pl->batch_stats.looped += (unsigned)list.size();
+		for (unsigned b : list)
+			if (int e = tspws_hip_stack(pl, p, d_x + h_first[b] * ld, ld, h_first[b + 1] - h_first[b], d_ls + (size_t)b * N, d_ts + (size_t)b * N, s)) return e;
+		return 0;
+	};
 	if (one.size() > 1 && tspws_many_trace_path(pl, n1)) {
 		pl->batch_stats.single_pass = (unsigned)one.size();
-		if ((rc = batch_single(pl, p, d_x, ld, h_first, one, n1, d_ls, d_ts, st, tab1))) return rc;
-	} else {
-		pl->batch_stats.looped += (unsigned)one.size();
-		for (unsigned b : one)
-			if ((rc = tspws_hip_stack(pl, p, d_x + h_first[b] * ld, ld, h_first[b + 1] - h_first[b], d_ls + (size_t)b * N, d_ts + (size_t)b * N, s))) return rc;
-	}
+		if ((rc = batch_single(pl, p, d_x, ld, h_first, one, n1, d_ls, d_ts, call))) return rc;
+	} else if ((rc = looped(one))) return rc;
 	if (two.size() > 1) {
 		pl->batch_stats.two_stage_pass = (unsigned)two.size();
-		if ((rc = batch_two_stage(pl, p, d_x, ld, h_first, two, n2, d_ls, d_ts, st, tab2))) return rc;
-	} else {
-		pl->batch_stats.looped += (unsigned)two.size();
-		for (unsigned b : two)
-			if ((rc = tspws_hip_stack(pl, p, d_x + h_first[b] * ld, ld, h_first[b + 1] - h_first[b], d_ls + (size_t)b * N, d_ts + (size_t)b * N, s))) return rc;
-	}
-	// empty ensembles: zero rows
-	for (unsigned b = 0; b < B; b++)
-		if (h_first[b + 1] == h_first[b]) {
-			HIP_TRY(hipMemsetAsync(d_ls + (size_t)b * N, 0, N * sizeof(float), st));
-			HIP_TRY(hipMemsetAsync(d_ts + (size_t)b * N, 0, N * sizeof(float), st));
-		}
+		if ((rc = batch_two_stage(pl, p, d_x, ld, h_first, two, n2, d_ls, d_ts, call, chunk_tabs))) return rc;
+	} else if ((rc = looped(two))) return rc;
+	if ((rc = zero_empty_ensembles(h_first, B, st, {{d_ls, N}, {d_ts, N}}))) return rc;
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st)); // outputs complete; the host tables of the uploads go out of scope
+	HIP_TRY(call.drain()); // outputs complete
 	return 0;
 }
 

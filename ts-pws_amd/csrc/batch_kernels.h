@@ -1,5 +1,6 @@
-// batch_kernels.h -- small kernels that the batched entry points share (batch.hip, jk_single.hip, jk_batch.hip).  Every unit that includes
-// this header gets its own copy (internal linkage: the units are compiled without relocatable device code).
+// batch_kernels.h -- small kernels that the batched entry points share: the gather of batch.hip and jk_batch.hip, the class time sums and the
+// replicas' finish (weighted sets, linear stacks) of jk_single.hip and jk_batch.hip, the per-row weight mode of those and sub_batch.hip.  Every
+// unit that includes this header gets its own copy (internal linkage: the units are compiled without relocatable device code).
 #pragma once
 
 #include "tspws_internal.h"
@@ -38,4 +39,67 @@ __device__ __forceinline__ int j1_weight_mode(double wu, int unbiased, unsigned 
 	if (wu == 2) return 0;
 	if (wu == 1) return 1;
 	return 2;
+}
+
+// One ensemble of a round to the replicas' finish below.  (jk_single.hip: ONE descriptor, everything but ncls zero, and no main rows.)
+struct JbEns { unsigned cls0, ncls, kept_off, kc_off, M, row; }; // classes [cls0, cls0 + ncls) of the round, kept[C][ncls] / K_c[C] offsets, traces, output row
+
+constexpr unsigned JB_NT = 64;      // coefficients per workgroup of k_jb_finish
+constexpr unsigned JB_RPB = 8;      // rows per workgroup
+constexpr unsigned JB_LDS_MAX = 24; // classes the LDS form holds (2 KB each: <= 48 KB of the CU's 160 KB, three workgroups resident)
+
+// Weighted coefficients of rows q0 + y, y < nq, of ensemble blockIdx.z of the round.  Rows of an ensemble: with `main`, row 0 = OUT and row 1 =
+// ST of the plain stack (all classes, K = M = M_b); then replica c = q - 2 main: ST_c / PS_c = sums of the kept classes' planes in class
+// order, OUT = ST_c * weight(PS_c; K = M = K_c).  One thread per coefficient (consecutive double2: coalesced),
+// RPB rows per workgroup; LDS: the coefficient's class values are staged once (each thread reads back only its own entries: no barrier).
+template <bool LDS>
+[[maybe_unused]] static __global__ void __launch_bounds__(JB_NT) k_jb_finish(const double2 *__restrict__ planes, size_t ncoef, const JbEns *__restrict__ ens,
+                                                     const char *__restrict__ kept, const unsigned *__restrict__ Kc, unsigned main, unsigned q0, unsigned nq,
+                                                     double wu, int unbiased, double2 *__restrict__ OUT)
+{
+	extern __shared__ double2 jb_sh[]; // [class][ST | PS][JB_NT]
+	const size_t i = (size_t)blockIdx.x * JB_NT + threadIdx.x;
+	if (i >= ncoef) return;
+	const JbEns e = ens[blockIdx.z];
+	const double2 *pl = planes + (size_t)e.cls0 * 2 * ncoef;
+	if (LDS)
+		for (unsigned k = 0; k < e.ncls; k++) {
+			jb_sh[(2 * k) * JB_NT + threadIdx.x] = pl[(size_t)k * 2 * ncoef + i];
+			jb_sh[(2 * k + 1) * JB_NT + threadIdx.x] = pl[(size_t)k * 2 * ncoef + ncoef + i];
+		}
+	const unsigned y1 = min(nq, (blockIdx.y + 1) * JB_RPB);
+	for (unsigned y = blockIdx.y * JB_RPB; y < y1; y++) {
+		const unsigned q = q0 + y;
+		const bool all = q < 2 * main;
+		const char *kr = kept + e.kept_off + (size_t)(all ? 0 : q - 2 * main) * e.ncls;
+		double2 st = make_double2(0, 0), ps = make_double2(0, 0);
+		for (unsigned k = 0; k < e.ncls; k++) {
+			if (!all && !kr[k]) continue; // (wave-uniform)
+			const double2 a = LDS ? jb_sh[(2 * k) * JB_NT + threadIdx.x] : pl[(size_t)k * 2 * ncoef + i];
+			const double2 b = LDS ? jb_sh[(2 * k + 1) * JB_NT + threadIdx.x] : pl[(size_t)k * 2 * ncoef + ncoef + i];
+			st.x += a.x; st.y += a.y; ps.x += b.x; ps.y += b.y;
+		}
+		double2 o;
+		if (all) o = q == 0 ? weight_value(st, ps, j1_weight_mode(wu, unbiased, e.M), (double)e.M, (double)e.M, wu) : st;
+		else {
+			const unsigned K = Kc[e.kc_off + q - 2 * main];
+			o = K ? weight_value(st, ps, j1_weight_mode(wu, unbiased, K), (double)K, (double)K, wu) : make_double2(0, 0);
+		}
+		OUT[((size_t)blockIdx.z * nq + y) * ncoef + i] = o;
+	}
+}
+
+// linear stacks of replicas c0 + blockIdx.y of ensemble blockIdx.z: (float)((sum of the kept classes' time sums) * (1 / K_c)), the
+// two-stage jackknife's time-domain formula (ts_pws1f_lib.c:799-811) with every trace its own group
+[[maybe_unused]] static __global__ void __launch_bounds__(256) k_jb_linear(const double *__restrict__ T, size_t N, const JbEns *__restrict__ ens, const char *__restrict__ kept,
+                                                   const unsigned *__restrict__ Kc, unsigned C, unsigned c0, float *__restrict__ out)
+{
+	const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (n >= N) return;
+	const JbEns e = ens[blockIdx.z];
+	const unsigned c = c0 + blockIdx.y, K = Kc[e.kc_off + c];
+	const char *kr = kept + e.kept_off + (size_t)c * e.ncls;
+	double acc = 0;
+	for (unsigned k = 0; k < e.ncls; k++) if (kr[k]) acc += T[(size_t)(e.cls0 + k) * N + n];
+	out[((size_t)e.row * C + c) * N + n] = K ? (float)(acc * (1.0 / (double)K)) : 0.f;
 }

@@ -23,6 +23,7 @@
 // the parts budget (TSPWS_PART_MB); a round of incremental steps may split an ensemble, the two-stage steps are independent, a round of the
 // linear curve holds whole ensembles (one alone may exceed the budget).  A batch with ONE non-empty ensemble is tspws_hip_convergence for it.
 #include "tspws_internal.h"
+#include "batch_host.h"
 
 namespace {
 
@@ -71,11 +72,7 @@ __global__ void __launch_bounds__(256) k_cb_prefix(const double2 *__restrict__ p
 	part += (size_t)(t0 - s0) * npart;
 	OUT += (size_t)(t0 - s0) * ncoef;
 	steps += t0;
-	unsigned lo = 0, hi = S;
-	while (hi - lo > 1) {
-		const unsigned mid = (lo + hi) >> 1;
-		if (sc[mid].acc2_off <= bx) lo = mid; else hi = mid;
-	}
+	const unsigned lo = find_block_scale(sc, S, bx, true);
 	const unsigned Ns = sc[lo].Ns, nsplit = sc[lo].nsplit;
 	if (nsplit > 1) {
 		// up to 32 partials per coefficient: the lanes of a wave are (8 traces) x (8 lanes that share the partials of a trace); the traces of a
@@ -312,7 +309,7 @@ extern "C" int tspws_hip_convergence_batch(tspws_hip_plan *pl, const t_tsPWS *p,
 
 	// rounds: every block that grows with the steps within the budget
 	const size_t budget = tspws_part_budget_bytes();
-	const size_t per_set = std::max({pl->npart * sizeof(double2), nc * sizeof(double2), (size_t)(pl->inv_noct + 1) * N * sizeof(double)});
+	const size_t per_set = std::max(pl->npart * sizeof(double2), tspws_inverse_row_bytes(pl));
 	const size_t nI = inc.size(), n2 = two.size(), nE = ens.size();
 	const size_t R1 = std::max<size_t>(1, std::min<size_t>({nI, budget / per_set, (size_t)65535 * (CB_CHAIN / 2)}));
 	const size_t per_step2 = std::max({(size_t)KM * pl->npart * sizeof(double2), (size_t)KM * N * sizeof(double), 2 * nc * sizeof(double2), per_set});
@@ -337,39 +334,40 @@ extern "C" int tspws_hip_convergence_batch(tspws_hip_plan *pl, const t_tsPWS *p,
 	chain_at.push_back(chain_tab.size());
 	// rounds of the linear curve: whole ensembles whose partial sums fit
 	const unsigned nblk = (unsigned)((N + 255) / 256);
-	struct LRound { size_t e0, e1, T; };
-	std::vector<LRound> lrounds;
+	std::vector<size_t> toff(nE + 1, 0); // traces in front of ensemble e
+	for (size_t e = 0; e < nE; e++) toff[e + 1] = toff[e] + ens[e].m;
+	const std::vector<Round> lrounds = whole_ensemble_rounds(nE, [&](size_t e0, size_t e1) {
+		return e1 - e0 <= 65535 && (toff[e1] - toff[e0]) * nblk * 3 * sizeof(double) <= budget;
+	});
 	size_t maxT = 0;
-	for (size_t e0 = 0, e1; e0 < nE; e0 = e1) {
-		size_t T = 0;
-		for (e1 = e0; e1 < nE && e1 - e0 < 65535 && (e1 == e0 || (T + ens[e1].m) * nblk * 3 * sizeof(double) <= budget); e1++) { ens[e1].off = (unsigned)T; T += ens[e1].m; }
-		lrounds.push_back({e0, e1, T});
-		maxT = std::max(maxT, T);
+	for (const Round &lr : lrounds) {
+		for (size_t e = lr.j0; e < lr.j1; e++) ens[e].off = (unsigned)(toff[e] - toff[lr.j0]);
+		maxT = std::max(maxT, toff[lr.j1] - toff[lr.j0]);
 	}
 
 	// the tables, in one block: incremental steps | two-stage steps | ensembles | their trace counts (doubles) | chains
-	const size_t o_two = nI * sizeof(CbStep), o_ens = o_two + n2 * sizeof(CbStep), o_mv = o_ens + nE * sizeof(CbEns), o_ch = o_mv + n2 * sizeof(double),
-	             tab_bytes = o_ch + chain_tab.size() * sizeof(unsigned);
+	TableLayout lay;
+	const size_t o_inc = lay.add<CbStep>(nI), o_two = lay.add<CbStep>(n2), o_ens = lay.add<CbEns>(nE), o_mv = lay.add<double>(n2),
+	             o_ch = lay.add<unsigned>(chain_tab.size()), tab_bytes = lay.bytes;
 	if (tab_bytes > budget) return fail(TSPWS_E_ARG, "convergence_batch: the step tables (24 bytes a trace) exceed TSPWS_PART_MB");
-	std::vector<char> blob(tab_bytes);
-	if (nI) memcpy(blob.data(), inc.data(), nI * sizeof(CbStep));
-	if (n2) memcpy(blob.data() + o_two, two.data(), n2 * sizeof(CbStep));
-	memcpy(blob.data() + o_ens, ens.data(), nE * sizeof(CbEns));
-	for (size_t q = 0; q < n2; q++) ((double *)(blob.data() + o_mv))[q] = (double)two[q].cnt;
-	memcpy(blob.data() + o_ch, chain_tab.data(), chain_tab.size() * sizeof(unsigned));
+	BatchCall call(st);
+	char *blob = call.block(tab_bytes), *tab;
+	if (nI) memcpy(blob + o_inc, inc.data(), nI * sizeof(CbStep));
+	if (n2) memcpy(blob + o_two, two.data(), n2 * sizeof(CbStep));
+	memcpy(blob + o_ens, ens.data(), nE * sizeof(CbEns));
+	for (size_t q = 0; q < n2; q++) ((double *)(blob + o_mv))[q] = (double)two[q].cnt;
+	memcpy(blob + o_ch, chain_tab.data(), chain_tab.size() * sizeof(unsigned));
 
 	// scratch, all of it before the first launch
 	const bool gather = KM != 0; // (without a two-stage rule the list is the trace array itself)
 	const size_t Rm = std::max(R1, R2);
-	if ((rc = scratch(pl, SCR_CBTAB, tab_bytes, &v))) return rc;
-	char *tab = (char *)v;
 	if ((rc = scratch(pl, SCR_PART, std::max<size_t>(2, std::max(R1, R2 * KM)) * pl->npart * sizeof(double2), &v))) return rc;
 	double2 *part = (double2 *)v;
 	float *xg = nullptr;
 	if (gather) { if ((rc = scratch(pl, SCR_CBX, R1 * N * sizeof(float), &v))) return rc; xg = (float *)v; }
-	if ((rc = scratch(pl, SCR_CBY, Rm * nc * sizeof(double2), &v))) return rc;
+	if ((rc = scratch(pl, SCR_ROWY, Rm * nc * sizeof(double2), &v))) return rc;
 	double2 *OUT = (double2 *)v;
-	if ((rc = scratch(pl, SCR_CBR, Rm * N * sizeof(double), &v))) return rc;
+	if ((rc = scratch(pl, SCR_ROWX, Rm * N * sizeof(double), &v))) return rc;
 	double *xr = (double *)v;
 	if ((rc = scratch(pl, SCR_CBST, (R2 + 2) * 2 * nc * sizeof(double2), &v))) return rc;
 	// the carried running pair twice (a round reads the one the last round wrote and writes the other: its first and last chain run side by
@@ -380,12 +378,11 @@ extern "C" int tspws_hip_convergence_batch(tspws_hip_plan *pl, const t_tsPWS *p,
 	if ((rc = scratch(pl, SCR_CBM, (Tn * 7 + B + (size_t)nblk * maxT * 3) * sizeof(double), &v))) return rc;
 	double *d_ts = (double *)v, *d_lin = d_ts + Tn * 4, *d_lsq = d_lin + Tn * 3, *d_lpart = d_lsq + B;
 
-	HIP_TRY(hipMemcpyAsync(tab, blob.data(), tab_bytes, hipMemcpyHostToDevice, st));
-	const CbStep *d_inc = (const CbStep *)tab, *d_two = (const CbStep *)(tab + o_two);
+	if ((rc = call.upload(pl, SCR_BTAB, blob, tab_bytes, &tab))) return rc;
+	const CbStep *d_inc = (const CbStep *)(tab + o_inc), *d_two = (const CbStep *)(tab + o_two);
 	const CbEns *d_ens = (const CbEns *)(tab + o_ens);
 	const double *d_Mv = (const double *)(tab + o_mv);
 	const unsigned *d_chain = (const unsigned *)(tab + o_ch);
-	auto sync_fail = [&](int code) { (void)hipStreamSynchronize(st); return code; }; // (`blob` goes out of scope)
 
 	// incremental steps
 	const int mode = tspws_weight_mode(p->wu, p->unbiased, 2), mode1 = tspws_weight_mode(p->wu, p->unbiased, 1);
@@ -401,10 +398,10 @@ extern "C" int tspws_hip_convergence_batch(tspws_hip_plan *pl, const t_tsPWS *p,
 				hipLaunchKernelGGL(k_cb_gather, dim3(nblk, (unsigned)std::min<size_t>(nb - g0, 65535)), dim3(256), 0, st, d_x, ld, N, first0, d_inc + q0 + g0, xg + g0 * N);
 			xb = xg; ldb = N;
 		}
-		if ((rc = tspws_forward_parts<float>(pl, xb, nb, ldb, part, st, nullptr, ScaleRange()))) return sync_fail(rc);
+		if ((rc = tspws_forward_parts<float>(pl, xb, nb, ldb, part, st, nullptr, ScaleRange()))) return rc;
 		hipLaunchKernelGGL(k_cb_prefix, dim3(pl->acc2_blocks, nchain), dim3(256), 0, st, (const double2 *)part, pl->npart, (const ScaleDesc *)pl->d_sc, pl->S, d_inc,
 		                   d_chain + chain_at[r], (unsigned)q0, OUT, nc, (const double2 *)carry + (r & 1) * 2 * nc, carry + ((r + 1) & 1) * 2 * nc, mode, mode1, p->wu);
-		if ((rc = tspws_hip_inverse(pl, (const double *)OUT, nb, xr, s))) return sync_fail(rc);
+		if ((rc = tspws_hip_inverse(pl, (const double *)OUT, nb, xr, s))) return rc;
 		hipLaunchKernelGGL(k_cb_dot4, dim3((unsigned)nb), dim3(1024), 0, st, (const double *)xr, d_inc + q0, d_ref_ts, N, d_ts, d_ts_steps);
 	}
 
@@ -416,30 +413,30 @@ extern "C" int tspws_hip_convergence_batch(tspws_hip_plan *pl, const t_tsPWS *p,
 		hipLaunchKernelGGL(k_cb_step_rows, dim3(nblk, (unsigned)nb), dim3(256), 0, st, d_x, ld, N, first0, d_two + q0, KM, rows);
 		FuseOut fz;
 		fz.accST = STr; fz.accPS = STr + nc; fz.stride = 2 * nc; fz.tps = KM;
-		if ((rc = tspws_forward_parts<double>(pl, rows, nb * KM, N, part, st, fuse ? &fz : nullptr, ScaleRange()))) return sync_fail(rc);
+		if ((rc = tspws_forward_parts<double>(pl, rows, nb * KM, N, part, st, fuse ? &fz : nullptr, ScaleRange()))) return rc;
 		WeightArgs wa;
 		wa.OUT = OUT; wa.out_stride = nc; wa.mode = tspws_weight_mode(p->wu, p->unbiased, KM); wa.K = (double)KM; wa.wu = p->wu; wa.Mv = d_Mv + q0;
 		tspws_launch_accumulate(pl, (const double2 *)part, KM, STr, STr + nc, 1, &fz, 1, st, (unsigned)nb, (size_t)KM * pl->npart, 2 * nc, nullptr, &wa, ScaleRange());
-		if ((rc = tspws_hip_inverse(pl, (const double *)OUT, nb, xr, s))) return sync_fail(rc);
+		if ((rc = tspws_hip_inverse(pl, (const double *)OUT, nb, xr, s))) return rc;
 		hipLaunchKernelGGL(k_cb_dot4, dim3((unsigned)nb), dim3(1024), 0, st, (const double *)xr, d_two + q0, d_ref_ts, N, d_ts, d_ts_steps);
 	}
 
 	// the linear curve
-	for (const LRound &lr : lrounds) {
-		const size_t dst0 = ens[lr.e0].dst;
-		hipLaunchKernelGGL(k_cb_linear, dim3(nblk, (unsigned)(lr.e1 - lr.e0)), dim3(256), 0, st, d_x, ld, N, d_ens + lr.e0, lr.T, d_ref_ls, d_lpart,
+	for (const Round &lr : lrounds) {
+		const size_t dst0 = ens[lr.j0].dst, T = toff[lr.j1] - toff[lr.j0];
+		hipLaunchKernelGGL(k_cb_linear, dim3(nblk, (unsigned)(lr.j1 - lr.j0)), dim3(256), 0, st, d_x, ld, N, d_ens + lr.j0, T, d_ref_ls, d_lpart,
 		                   d_ls_steps);
-		hipLaunchKernelGGL(k_cb_lin_reduce, dim3((unsigned)((lr.T * 3 + 255) / 256)), dim3(256), 0, st, (const double *)d_lpart, nblk, lr.T, d_lin + dst0 * 3);
+		hipLaunchKernelGGL(k_cb_lin_reduce, dim3((unsigned)((T * 3 + 255) / 256)), dim3(256), 0, st, (const double *)d_lpart, nblk, T, d_lin + dst0 * 3);
 	}
 	hipLaunchKernelGGL(k_cb_refsq, dim3(B), dim3(1024), 0, st, d_ref_ls, N, d_lsq);
-	if (hipGetLastError() != hipSuccess) return sync_fail(fail(TSPWS_E_HIP, "convergence_batch: launch"));
+	if (hipGetLastError() != hipSuccess) return fail(TSPWS_E_HIP, "convergence_batch: launch");
 
 	// one copy per curve
 	std::vector<double> hts(Tn * 4), hl(Tn * 3), lsq(B);
 	hipError_t e1 = hipMemcpyAsync(hts.data(), d_ts, Tn * 4 * sizeof(double), hipMemcpyDeviceToHost, st);
 	hipError_t e2 = hipMemcpyAsync(hl.data(), d_lin, Tn * 3 * sizeof(double), hipMemcpyDeviceToHost, st);
 	hipError_t e3 = hipMemcpyAsync(lsq.data(), d_lsq, B * sizeof(double), hipMemcpyDeviceToHost, st);
-	hipError_t e4 = hipStreamSynchronize(st);
+	hipError_t e4 = call.drain();
 	for (hipError_t e : {e1, e2, e3, e4})
 		if (e != hipSuccess) return fail(TSPWS_E_HIP, "convergence_batch: copy to the host", e);
 	for (const CbEns &e : ens)

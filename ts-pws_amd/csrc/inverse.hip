@@ -222,6 +222,13 @@ bool tspws_generic_inverse()
 // The waves [w0, w1) of the polyphase inverse's launch list for nb NREC-set reconstructions (grid.y) on `st`, into the octave buffer (*obuf: inv_nslots
 // rows per set): the LDS-staged instantiation below the LDS bound, the per-lane one up to inv_waves_fast, the GEN one above.
 static unsigned inv_nslots(const tspws_hip_plan *p) { return p->inv_noct + (p->inv_ngeneric ? 1 : 0); }
+// Bytes that one row (coefficient set) of a batched tspws_hip_inverse costs in its largest block: the set itself, its reconstruction, or its
+// share of the octave buffer below (N doubles per octave item, + 1 for the generic scales whether or not the frame has any: an upper bound).
+// What the batched units size their finish batches by.
+size_t tspws_inverse_row_bytes(const tspws_hip_plan *p)
+{
+	return std::max({p->ncoef * sizeof(double2), (size_t)p->N * sizeof(double), (size_t)(p->inv_noct + 1) * p->N * sizeof(double)});
+}
 template <int NREC>
 static int inv_launch_waves(tspws_hip_plan *p, const double2 *Y, unsigned nb, unsigned w0, unsigned w1, hipStream_t st, double **obuf)
 {

@@ -21,18 +21,13 @@
 // the many-trace path is one tspws_hip_stack + tspws_hip_jackknife_single per ensemble.
 #include "tspws_internal.h"
 #include "batch_kernels.h"
-#include <unordered_map>
+#include "batch_host.h"
 
 #define is_two_stage tspws_is_two_stage
 
 namespace {
 
 struct JbSeg { unsigned blk, nblk, ntr, cls, head; };           // blocks [blk, blk + nblk) of a pass batch hold ntr traces of class cls (of the round)
-struct JbEns { unsigned cls0, ncls, kept_off, kc_off, M, row; }; // classes [cls0, cls0 + ncls) of the round, kept[C][ncls] / K_c[C] offsets, traces, output row
-
-constexpr unsigned JB_NT = 64;      // coefficients per workgroup of k_jb_finish
-constexpr unsigned JB_RPB = 8;      // rows per workgroup
-constexpr unsigned JB_LDS_MAX = 24; // classes the LDS form holds (2 KB each: <= 48 KB of the CU's 160 KB, three workgroups resident)
 
 } // namespace
 
@@ -44,11 +39,7 @@ __global__ void __launch_bounds__(256) k_jb_accumulate(const double2 *__restrict
                                                        double2 *__restrict__ planes)
 {
 	const JbSeg s = seg[blockIdx.y];
-	unsigned lo = 0, hi = S;
-	while (hi - lo > 1) {
-		const unsigned mid = (lo + hi) >> 1;
-		if (sc[mid].acc2_off <= blockIdx.x) lo = mid; else hi = mid;
-	}
+	const unsigned lo = find_block_scale(sc, S, blockIdx.x, true);
 	const unsigned Ns = sc[lo].Ns, nsplit = sc[lo].nsplit;
 	double2 *ST = planes + (size_t)s.cls * 2 * ncoef, *PS = ST + ncoef;
 	if (sc[lo].fuse_ok) {
@@ -84,47 +75,6 @@ __global__ void __launch_bounds__(256) k_jb_accumulate(const double2 *__restrict
 	}
 }
 
-// Weighted coefficients of rows q0 + y, y < nq, of ensemble blockIdx.z of the round.  Rows of an ensemble: with `main`, row 0 = OUT and row 1 =
-// ST of the plain stack (all classes, K = M = M_b); then replica c = q - 2 main: ST_c / PS_c = sums of the kept classes' planes in class
-// order, OUT = ST_c * weight(PS_c; K = M = K_c) (k_j1_finish over ensembles).  One thread per coefficient (consecutive double2: coalesced),
-// RPB rows per workgroup; LDS: the coefficient's class values are staged once (each thread reads back only its own entries: no barrier).
-template <bool LDS>
-__global__ void __launch_bounds__(JB_NT) k_jb_finish(const double2 *__restrict__ planes, size_t ncoef, const JbEns *__restrict__ ens,
-                                                     const char *__restrict__ kept, const unsigned *__restrict__ Kc, unsigned main, unsigned q0, unsigned nq,
-                                                     double wu, int unbiased, double2 *__restrict__ OUT)
-{
-	extern __shared__ double2 jb_sh[]; // [class][ST | PS][JB_NT]
-	const size_t i = (size_t)blockIdx.x * JB_NT + threadIdx.x;
-	if (i >= ncoef) return;
-	const JbEns e = ens[blockIdx.z];
-	const double2 *pl = planes + (size_t)e.cls0 * 2 * ncoef;
-	if (LDS)
-		for (unsigned k = 0; k < e.ncls; k++) {
-			jb_sh[(2 * k) * JB_NT + threadIdx.x] = pl[(size_t)k * 2 * ncoef + i];
-			jb_sh[(2 * k + 1) * JB_NT + threadIdx.x] = pl[(size_t)k * 2 * ncoef + ncoef + i];
-		}
-	const unsigned y1 = min(nq, (blockIdx.y + 1) * JB_RPB);
-	for (unsigned y = blockIdx.y * JB_RPB; y < y1; y++) {
-		const unsigned q = q0 + y;
-		const bool all = q < 2 * main;
-		const char *kr = kept + e.kept_off + (size_t)(all ? 0 : q - 2 * main) * e.ncls;
-		double2 st = make_double2(0, 0), ps = make_double2(0, 0);
-		for (unsigned k = 0; k < e.ncls; k++) {
-			if (!all && !kr[k]) continue; // (wave-uniform)
-			const double2 a = LDS ? jb_sh[(2 * k) * JB_NT + threadIdx.x] : pl[(size_t)k * 2 * ncoef + i];
-			const double2 b = LDS ? jb_sh[(2 * k + 1) * JB_NT + threadIdx.x] : pl[(size_t)k * 2 * ncoef + ncoef + i];
-			st.x += a.x; st.y += a.y; ps.x += b.x; ps.y += b.y;
-		}
-		double2 o;
-		if (all) o = q == 0 ? weight_value(st, ps, j1_weight_mode(wu, unbiased, e.M), (double)e.M, (double)e.M, wu) : st;
-		else {
-			const unsigned K = Kc[e.kc_off + q - 2 * main];
-			o = K ? weight_value(st, ps, j1_weight_mode(wu, unbiased, K), (double)K, (double)K, wu) : make_double2(0, 0);
-		}
-		OUT[((size_t)blockIdx.z * nq + y) * ncoef + i] = o;
-	}
-}
-
 // float outputs of the rows of k_jb_finish after the inverse: x[(z nq + y)][n] = reconstruction of row q0 + y of ensemble z.  Main rows:
 // tsPWS = (float) ICWT(OUT), ls = (float) ICWT(ST) / (float) M_b (ts_pws1f_lib.c:233-241); replicas: tsPWS_out = (float) x (zero rows for K_c = 0)
 __global__ void __launch_bounds__(256) k_jb_epilogue(const double *__restrict__ x, size_t N, const JbEns *__restrict__ ens, const unsigned *__restrict__ Kc,
@@ -145,39 +95,7 @@ __global__ void __launch_bounds__(256) k_jb_epilogue(const double *__restrict__ 
 	}
 }
 
-// linear stacks of replicas c0 + blockIdx.y of ensemble blockIdx.z: (float)((sum of the kept classes' time sums) * (1 / K_c)) (k_j1_linear over ensembles)
-__global__ void __launch_bounds__(256) k_jb_linear(const double *__restrict__ T, size_t N, const JbEns *__restrict__ ens, const char *__restrict__ kept,
-                                                   const unsigned *__restrict__ Kc, unsigned C, unsigned c0, float *__restrict__ out)
-{
-	const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
-	if (n >= N) return;
-	const JbEns e = ens[blockIdx.z];
-	const unsigned c = c0 + blockIdx.y, K = Kc[e.kc_off + c];
-	const char *kr = kept + e.kept_off + (size_t)c * e.ncls;
-	double acc = 0;
-	for (unsigned k = 0; k < e.ncls; k++) if (kr[k]) acc += T[(size_t)(e.cls0 + k) * N + n];
-	out[((size_t)e.row * C + c) * N + n] = K ? (float)(acc * (1.0 / (double)K)) : 0.f;
-}
-
 namespace {
-
-// classes of the columns [col0, col0 + m) of sel[C][T] (tspws_selection_classes' rule: identical columns, first-appearance order)
-void strided_classes(const char *sel, unsigned C, size_t T, size_t col0, size_t m, std::vector<unsigned> &cls, std::vector<size_t> &first)
-{
-	const size_t nbytes = ((size_t)C + 7) / 8;
-	std::unordered_map<std::string, unsigned> id;
-	std::string key(nbytes, '\0');
-	cls.resize(m);
-	first.clear();
-	for (size_t i = 0; i < m; i++) {
-		std::fill(key.begin(), key.end(), '\0');
-		for (unsigned c = 0; c < C; c++)
-			if (sel[(size_t)c * T + col0 + i] == 1) key[c >> 3] = (char)(key[c >> 3] | (1 << (c & 7)));
-		auto it = id.find(key);
-		if (it == id.end()) { it = id.emplace(key, (unsigned)first.size()).first; first.push_back(i); }
-		cls[i] = it->second;
-	}
-}
 
 struct Ens { unsigned b; size_t f, m, cls0, ncls, kept_off; }; // ensemble with traces: index, first trace, traces, classes [cls0, cls0 + ncls) of the call, kept[C][ncls]
 
@@ -189,10 +107,21 @@ struct Layout {
 	std::vector<char> kept;       // per ensemble [C][ncls]
 };
 
+// the tables of a round in one block: gather slots | ensembles | segments of every batch of the pass | idx | cptr | K_c | kept
+struct JbTab { size_t src, ens, seg, idx, cp, kc, kept, bytes; };
+JbTab jb_tab(size_t nslots, size_t ne, size_t nseg, size_t ntr, size_t ncl, size_t nkc, size_t nkept)
+{
+	TableLayout lay;
+	const size_t src = lay.add<long long>(nslots), ens = lay.add<JbEns>(ne), seg = lay.add<JbSeg>(nseg), idx = lay.add<unsigned>(ntr),
+	             cp = lay.add<unsigned>(ncl + 1), kc = lay.add<unsigned>(nkc), kept = lay.add<char>(nkept);
+	return {src, ens, seg, idx, cp, kc, kept, lay.bytes};
+}
+
 int shared_pass(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const Layout &L, size_t total, unsigned C, bool main, float *d_ls,
-                float *d_ts, float *d_ls_out, float *d_ts_out, const unsigned *h_Kc, hipStream_t st, std::vector<std::vector<char>> &keep)
+                float *d_ts, float *d_ls_out, float *d_ts_out, const unsigned *h_Kc, BatchCall &call)
 {
 	const size_t N = pl->N, nc = pl->ncoef, n = L.ens.size(), G = L.cptr.size() - 1;
+	hipStream_t st = call.stream();
 	const size_t budget = tspws_part_budget_bytes();
 	const unsigned RPE = C + (main ? 2u : 0u); // rows of an ensemble
 	int rc;
@@ -206,51 +135,39 @@ int shared_pass(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t l
 
 	// rounds of whole ensembles: class planes, time sums, two rows per ensemble of sets / reconstructions / octave buffer and the tables within
 	// the budget; at most 65535 classes and ensembles (grid.y / grid.z)
-	const size_t per_row = std::max({nc * sizeof(double2), N * sizeof(double), (size_t)(pl->inv_noct + 1) * N * sizeof(double)});
-	auto tab_bytes = [&](size_t j0, size_t j1) { // (an upper bound: a class has at most one segment per batch it touches)
-		const size_t g0 = L.ens[j0].cls0, g1 = L.ens[j1 - 1].cls0 + L.ens[j1 - 1].ncls, nblk = L.blk0[g1] - L.blk0[g0];
-		return nblk * 64 * sizeof(long long) + (j1 - j0) * (sizeof(JbEns) + (size_t)C * 4) + ((g1 - g0) + nblk / bpb + 2) * sizeof(JbSeg) +
-		       (L.cptr[g1] - L.cptr[g0] + (g1 - g0) + 1) * 4 + (size_t)C * (g1 - g0) + 64;
+	const size_t per_row = tspws_inverse_row_bytes(pl);
+	auto cls_end = [&](size_t j) { return L.ens[j].cls0 + L.ens[j].ncls; };
+	auto tab_bound = [&](size_t j0, size_t j1) { // (a class has at most one segment per batch it touches)
+		const size_t g0 = L.ens[j0].cls0, ncl = cls_end(j1 - 1) - g0, nblk = L.blk0[g0 + ncl] - L.blk0[g0];
+		return jb_tab(nblk * 64, j1 - j0, ncl + nblk / bpb + 2, L.cptr[g0 + ncl] - L.cptr[g0], ncl, (j1 - j0) * C, (size_t)C * ncl).bytes;
 	};
-	struct Round { size_t j0, j1; };
-	std::vector<Round> rounds;
-	size_t max_cls = 0, max_ne = 0, max_tab = 0;
-	for (size_t j0 = 0, j1; j0 < n; j0 = j1) {
-		j1 = j0 + 1;
-		while (j1 < n) {
-			const size_t ncl = L.ens[j1].cls0 + L.ens[j1].ncls - L.ens[j0].cls0, ne = j1 + 1 - j0;
-			if (ncl > 65535 || ne > 65535 || ncl * 2 * nc * sizeof(double2) > budget || ncl * N * sizeof(double) > budget || ne * 2 * per_row > budget ||
-			    tab_bytes(j0, j1 + 1) > budget)
-				break;
-			j1++;
-		}
-		rounds.push_back({j0, j1});
-		max_cls = std::max(max_cls, L.ens[j1 - 1].cls0 + L.ens[j1 - 1].ncls - L.ens[j0].cls0);
-		max_ne = std::max(max_ne, j1 - j0);
-		max_tab = std::max(max_tab, tab_bytes(j0, j1));
+	const std::vector<Round> rounds = whole_ensemble_rounds(n, [&](size_t j0, size_t j1) {
+		const size_t ncl = cls_end(j1 - 1) - L.ens[j0].cls0, ne = j1 - j0;
+		return !(ncl > 65535 || ne > 65535 || ncl * 2 * nc * sizeof(double2) > budget || ncl * N * sizeof(double) > budget || ne * 2 * per_row > budget ||
+		         tab_bound(j0, j1) > budget);
+	});
+	// rows per ensemble and finish batch
+	auto rows_per_batch = [&](size_t ne) { return (unsigned)even_rows_per_batch(budget, ne * per_row, RPE); };
+	size_t max_cls = 0, max_rows = 0, max_tab = 0;
+	for (const Round &r : rounds) {
+		max_cls = std::max(max_cls, cls_end(r.j1 - 1) - L.ens[r.j0].cls0);
+		max_rows = std::max(max_rows, (r.j1 - r.j0) * rows_per_batch(r.j1 - r.j0));
+		max_tab = std::max(max_tab, tab_bound(r.j0, r.j1));
 	}
-	// rows per ensemble and finish batch: even (the inverse pairs the same rows whatever the batching), the sets and reconstructions within the budget
-	auto rows_per_batch = [&](size_t ne) {
-		return (unsigned)std::min<size_t>({RPE, 65534, std::max<size_t>(2, (budget / (ne * per_row)) & ~(size_t)1)}); // (65534: grid.y of k_jb_epilogue)
-	};
-	size_t max_rows = 0;
-	for (const Round &r : rounds) max_rows = std::max(max_rows, (r.j1 - r.j0) * rows_per_batch(r.j1 - r.j0));
 	if ((rc = scratch(pl, SCR_JBPL, max_cls * 2 * nc * sizeof(double2), &v))) return rc;
 	double2 *planes = (double2 *)v;
 	if ((rc = scratch(pl, SCR_JBT, max_cls * N * sizeof(double), &v))) return rc;
 	double *Tsum = (double *)v;
-	if ((rc = scratch(pl, SCR_JBY, max_rows * nc * sizeof(double2), &v))) return rc;
+	if ((rc = scratch(pl, SCR_ROWY, max_rows * nc * sizeof(double2), &v))) return rc;
 	double2 *OUT = (double2 *)v;
-	if ((rc = scratch(pl, SCR_JBX, max_rows * N * sizeof(double), &v))) return rc;
+	if ((rc = scratch(pl, SCR_ROWX, max_rows * N * sizeof(double), &v))) return rc;
 	double *xr = (double *)v;
-	if ((rc = scratch(pl, SCR_JBTAB, max_tab, &v))) return rc;
-	char *tab = (char *)v;
 
 	for (const Round &r : rounds) {
-		const size_t ne = r.j1 - r.j0, g0 = L.ens[r.j0].cls0, g1 = L.ens[r.j1 - 1].cls0 + L.ens[r.j1 - 1].ncls, ncl = g1 - g0;
+		const size_t ne = r.j1 - r.j0, g0 = L.ens[r.j0].cls0, g1 = cls_end(r.j1 - 1), ncl = g1 - g0;
 		const size_t b0 = L.blk0[g0], b1 = L.blk0[g1], q0r = L.cptr[g0], ntr = L.cptr[g1] - q0r;
 		pl->jk_batch_stats.rounds++;
-		// the round's tables: gather slots | ensembles | segments of every batch of the pass | idx | cptr | K_c | kept
+		// the round's tables
 		std::vector<JbSeg> segs;
 		std::vector<size_t> seg0; // segments of batch k: [seg0[k], seg0[k + 1])
 		for (size_t c0 = b0; c0 < b1; c0 += bpb) {
@@ -267,17 +184,13 @@ int shared_pass(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t l
 			}
 		}
 		seg0.push_back(segs.size());
-		const size_t o_ens = (b1 - b0) * 64 * sizeof(long long), o_seg = o_ens + ne * sizeof(JbEns), o_idx = o_seg + segs.size() * sizeof(JbSeg),
-		             o_cp = o_idx + ntr * 4, o_kc = o_cp + (ncl + 1) * 4, o_kp = o_kc + ne * (size_t)C * 4;
-		size_t kp_bytes = 0;
-		for (size_t j = r.j0; j < r.j1; j++) kp_bytes += (size_t)C * L.ens[j].ncls;
-		keep.emplace_back(o_kp + kp_bytes + 1, 0);
-		char *blob = keep.back().data();
-		if (keep.back().size() > max_tab) return fail(TSPWS_E_ARG, "jackknife_batch: table bound"); // (cannot happen: tab_bytes is an upper bound)
-		long long *src = (long long *)blob;
-		JbEns *he = (JbEns *)(blob + o_ens);
-		unsigned *hidx = (unsigned *)(blob + o_idx), *hcp = (unsigned *)(blob + o_cp), *hkc = (unsigned *)(blob + o_kc);
-		if (!segs.empty()) memcpy(blob + o_seg, segs.data(), segs.size() * sizeof(JbSeg));
+		const JbTab o = jb_tab((b1 - b0) * 64, ne, segs.size(), ntr, ncl, ne * C, (size_t)C * ncl);
+		if (o.bytes > max_tab) return fail(TSPWS_E_ARG, "jackknife_batch: table bound"); // (cannot happen: tab_bound is an upper bound)
+		char *blob = call.block(o.bytes), *tab;
+		long long *src = (long long *)(blob + o.src);
+		JbEns *he = (JbEns *)(blob + o.ens);
+		unsigned *hidx = (unsigned *)(blob + o.idx), *hcp = (unsigned *)(blob + o.cp), *hkc = (unsigned *)(blob + o.kc);
+		if (!segs.empty()) memcpy(blob + o.seg, segs.data(), segs.size() * sizeof(JbSeg));
 		for (size_t g = g0; g < g1; g++) {
 			const size_t m = L.cptr[g + 1] - L.cptr[g];
 			for (size_t i = 0; i < (L.blk0[g + 1] - L.blk0[g]) * 64; i++) src[(L.blk0[g] - b0) * 64 + i] = i < m ? (long long)L.idx[L.cptr[g] + i] : -1;
@@ -294,16 +207,16 @@ int shared_pass(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t l
 			d.M = (unsigned)e.m; d.row = e.b;
 			he[j - r.j0] = d;
 			memcpy(hkc + (j - r.j0) * (size_t)C, h_Kc + (size_t)e.b * C, (size_t)C * 4);
-			memcpy(blob + o_kp + kp, L.kept.data() + e.kept_off, (size_t)C * e.ncls);
+			memcpy(blob + o.kept + kp, L.kept.data() + e.kept_off, (size_t)C * e.ncls);
 			kp += (size_t)C * e.ncls;
 			max_ncls = std::max(max_ncls, d.ncls);
 		}
-		HIP_TRY(hipMemcpyAsync(tab, blob, keep.back().size(), hipMemcpyHostToDevice, st));
-		const long long *d_src = (const long long *)tab;
-		const JbEns *d_ens = (const JbEns *)(tab + o_ens);
-		const JbSeg *d_seg = (const JbSeg *)(tab + o_seg);
-		const unsigned *d_idx = (const unsigned *)(tab + o_idx), *d_cp = (const unsigned *)(tab + o_cp), *d_kc = (const unsigned *)(tab + o_kc);
-		const char *d_kept = tab + o_kp;
+		if ((rc = call.upload(pl, SCR_BTAB, blob, o.bytes, &tab, max_tab))) return rc;
+		const long long *d_src = (const long long *)(tab + o.src);
+		const JbEns *d_ens = (const JbEns *)(tab + o.ens);
+		const JbSeg *d_seg = (const JbSeg *)(tab + o.seg);
+		const unsigned *d_idx = (const unsigned *)(tab + o.idx), *d_cp = (const unsigned *)(tab + o.cp), *d_kc = (const unsigned *)(tab + o.kc);
+		const char *d_kept = tab + o.kept;
 
 		// class pass: the round's blocks in batches of the pass (whole blocks: a class may straddle two batches)
 		size_t kb = 0;
@@ -371,7 +284,8 @@ extern "C" int tspws_hip_jackknife_batch(tspws_hip_plan *pl, const t_tsPWS *p, c
 	for (unsigned b = 0; b < B; b++) {
 		const size_t f = h_first[b], m = h_first[b + 1] - f, col0 = f - h_first[0];
 		if (!m) { nempty++; continue; }
-		strided_classes(h_sel, C, Tn, col0, m, cls, firsts);
+		cls.resize(m);
+		selection_classes_strided(h_sel, C, Tn, col0, m, cls.data(), firsts);
 		const size_t ncls = firsts.size();
 		if (ncls > 65535) return fail(TSPWS_E_ARG, "jackknife_batch: more than 65535 distinct selection columns in one ensemble");
 		Ens e;
@@ -398,12 +312,7 @@ extern "C" int tspws_hip_jackknife_batch(tspws_hip_plan *pl, const t_tsPWS *p, c
 	// replica sizes
 	for (unsigned b = 0; b < B; b++) {
 		const size_t col0 = h_first[b] - h_first[0], m = h_first[b + 1] - h_first[b];
-		for (unsigned c = 0; c < C; c++) {
-			const char *row = h_sel + (size_t)c * Tn + col0;
-			unsigned k = 0;
-			for (size_t i = 0; i < m; i++) k += row[i] == 1;
-			h_mtr_out[(size_t)b * C + c] = k;
-		}
+		for (unsigned c = 0; c < C; c++) h_mtr_out[(size_t)b * C + c] = kept_count(h_sel + (size_t)c * Tn + col0, m);
 	}
 	HIP_TRY(hipSetDevice(pl->device));
 	hipStream_t st = S_(s);
@@ -411,34 +320,23 @@ extern "C" int tspws_hip_jackknife_batch(tspws_hip_plan *pl, const t_tsPWS *p, c
 	pl->jk_batch_stats = tspws_hip_jk_batch_stats();
 	pl->jk_batch_stats.empty = nempty;
 	pl->jk_batch_stats.classes = (unsigned)(L.cptr.size() - 1);
-	std::vector<std::vector<char>> keep; // host sources of the uploads: alive until the final synchronisation
+	BatchCall call(st);
 	if (!L.ens.empty() && tspws_many_trace_path(pl, Tn)) {
 		pl->jk_batch_stats.shared = (unsigned)L.ens.size();
-		if ((rc = shared_pass(pl, p, d_x, ld, L, Tn, C, main, d_ls, d_ts, d_ls_out, d_ts_out, h_mtr_out, st, keep))) return rc;
+		if ((rc = shared_pass(pl, p, d_x, ld, L, Tn, C, main, d_ls, d_ts, d_ls_out, d_ts_out, h_mtr_out, call))) return rc;
 	} else {
 		pl->jk_batch_stats.looped = (unsigned)L.ens.size();
-		std::vector<char> sel;
 		for (const Ens &e : L.ens) {
-			sel.resize((size_t)C * e.m);
-			for (unsigned c = 0; c < C; c++) memcpy(sel.data() + (size_t)c * e.m, h_sel + (size_t)c * Tn + (e.f - h_first[0]), e.m);
+			const char *sel = ensemble_selection(call, h_sel, C, Tn, e.f - h_first[0], e.m);
 			if (main && (rc = tspws_hip_stack(pl, p, d_x + e.f * ld, ld, e.m, d_ls + (size_t)e.b * N, d_ts + (size_t)e.b * N, s))) return rc;
-			if ((rc = tspws_hip_jackknife_single(pl, p, d_x + e.f * ld, ld, e.m, sel.data(), C, d_ls_out + (size_t)e.b * C * N, d_ts_out + (size_t)e.b * C * N,
+			if ((rc = tspws_hip_jackknife_single(pl, p, d_x + e.f * ld, ld, e.m, sel, C, d_ls_out + (size_t)e.b * C * N, d_ts_out + (size_t)e.b * C * N,
 			                                     h_mtr_out + (size_t)e.b * C, s)))
 				return rc;
 		}
 	}
-	// empty ensembles: zero rows
-	for (unsigned b = 0; b < B; b++)
-		if (h_first[b + 1] == h_first[b]) {
-			HIP_TRY(hipMemsetAsync(d_ls_out + (size_t)b * C * N, 0, (size_t)C * N * sizeof(float), st));
-			HIP_TRY(hipMemsetAsync(d_ts_out + (size_t)b * C * N, 0, (size_t)C * N * sizeof(float), st));
-			if (main) {
-				HIP_TRY(hipMemsetAsync(d_ls + (size_t)b * N, 0, N * sizeof(float), st));
-				HIP_TRY(hipMemsetAsync(d_ts + (size_t)b * N, 0, N * sizeof(float), st));
-			}
-		}
+	if ((rc = zero_empty_ensembles(h_first, B, st, {{d_ls_out, (size_t)C * N}, {d_ts_out, (size_t)C * N}, {d_ls, N}, {d_ts, N}}))) return rc;
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st)); // outputs complete; the host tables of the uploads go out of scope
+	HIP_TRY(call.drain()); // outputs complete
 	return 0;
 }
 

@@ -22,6 +22,7 @@
 // buffer, tables -- within the parts budget (TSPWS_PART_MB); a round never splits an ensemble, one ensemble alone may exceed it.  A batch with
 // ONE non-empty ensemble is tspws_hip_stack_jackknife (tspws_hip_jackknife without the main rows) for it.
 #include "tspws_internal.h"
+#include "batch_host.h"
 
 #define is_two_stage tspws_is_two_stage
 
@@ -302,33 +303,37 @@ void build_tile(const char *h_sel, size_t Tn, size_t col0, const Ens &e, unsigne
 	}
 }
 
+// the tables of a round in one block: trace counts of the nsl slices (doubles) | runs | (ensemble, tile) run ranges | flush rows | counts | output rows
+struct J2Tab { size_t mv, run, wg, fl, cnt, row, bytes; };
+J2Tab j2_tab(size_t nsl, size_t nruns, size_t nwg, size_t nfl)
+{
+	TableLayout lay;
+	const size_t mv = lay.add<double>(nsl), run = lay.add<RunDesc>(nruns), wg = lay.add<J2Wg>(nwg), fl = lay.add<unsigned>(nfl), cnt = lay.add<unsigned>(nsl),
+	             row = lay.add<unsigned>(nsl);
+	return {mv, run, wg, fl, cnt, row, lay.bytes};
+}
+
 int shared_walk(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const Tables &T, unsigned C, bool main, unsigned ntile, float *d_ls,
-                float *d_ts, float *d_ls_out, float *d_ts_out, const unsigned *h_Kc, hipStream_t st, std::vector<std::vector<char>> &keep,
-                tspws_hip_jk_batch2_stats *stats)
+                float *d_ts, float *d_ls_out, float *d_ts_out, const unsigned *h_Kc, BatchCall &call, tspws_hip_jk_batch2_stats *stats)
 {
 	const size_t N = pl->N, nc = pl->ncoef, n = T.ens.size(), budget = tspws_part_budget_bytes();
+	hipStream_t st = call.stream();
 	const unsigned KM = p->Kmax, W = C + (main ? 1u : 0u);
 	int rc;
 	void *v;
 	// rounds of whole ensembles: the rows, their partials, the plane pairs, the weighted sets / reconstructions / octave buffer of the W (+ 1: the
 	// plain stack's ST) sets of an ensemble and the tables within the budget; slices and sets within grid.y, ensembles within grid.z
-	const size_t per_set = std::max({nc * sizeof(double2), N * sizeof(double), (size_t)(pl->inv_noct + 1) * N * sizeof(double)});
 	const size_t per_ens = std::max({(size_t)W * KM * N * sizeof(double), (size_t)W * KM * pl->npart * sizeof(double2), (size_t)W * 2 * nc * sizeof(double2),
-	                                 (size_t)(W + 1) * per_set});
+	                                 (size_t)(W + 1) * tspws_inverse_row_bytes(pl)});
 	const size_t R = std::max<size_t>(1, std::min<size_t>({budget / per_ens, 65535 / ((size_t)W + 1), 0xffffffffull / ((size_t)W * KM)}));
-	auto tab_bytes = [&](size_t j0, size_t j1) {
-		return (j1 - j0) * W * (sizeof(double) + 8) + (T.run_ptr[j1 * ntile] - T.run_ptr[j0 * ntile]) * sizeof(RunDesc) + (j1 - j0) * ntile * sizeof(J2Wg) +
-		       (T.flush_ptr[j1] - T.flush_ptr[j0]) * 4 + 64;
+	auto tab_of = [&](size_t j0, size_t j1) {
+		return j2_tab((j1 - j0) * W, T.run_ptr[j1 * ntile] - T.run_ptr[j0 * ntile], (j1 - j0) * ntile, T.flush_ptr[j1] - T.flush_ptr[j0]);
 	};
-	struct Round { size_t j0, j1; };
-	std::vector<Round> rounds;
+	const std::vector<Round> rounds = whole_ensemble_rounds(n, [&](size_t j0, size_t j1) { return j1 - j0 <= R && tab_of(j0, j1).bytes <= budget; });
 	size_t max_ne = 0, max_tab = 0;
-	for (size_t j0 = 0, j1; j0 < n; j0 = j1) {
-		j1 = j0 + 1;
-		while (j1 < n && j1 - j0 < R && tab_bytes(j0, j1 + 1) <= budget) j1++;
-		rounds.push_back({j0, j1});
-		max_ne = std::max(max_ne, j1 - j0);
-		max_tab = std::max(max_tab, tab_bytes(j0, j1));
+	for (const Round &r : rounds) {
+		max_ne = std::max(max_ne, r.j1 - r.j0);
+		max_tab = std::max(max_tab, tab_of(r.j0, r.j1).bytes);
 	}
 	if ((size_t)W * KM > 0xffffffffull || max_ne * W * KM > 0xffffffffull) return fail(TSPWS_E_ARG, "jackknife_batch_two_stage: more than 2^32 partial-stack rows in a round");
 	const size_t max_sl = max_ne * W, max_sets = max_ne * (W + (main ? 1u : 0u));
@@ -338,12 +343,10 @@ int shared_walk(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t l
 	double2 *part = (double2 *)v;
 	if ((rc = scratch(pl, SCR_J2ST, max_sl * 2 * nc * sizeof(double2), &v))) return rc;
 	double2 *STr = (double2 *)v;
-	if ((rc = scratch(pl, SCR_J2Y, max_sets * nc * sizeof(double2), &v))) return rc;
+	if ((rc = scratch(pl, SCR_ROWY, max_sets * nc * sizeof(double2), &v))) return rc;
 	double2 *OUT = (double2 *)v;
-	if ((rc = scratch(pl, SCR_J2X, max_sets * N * sizeof(double), &v))) return rc;
+	if ((rc = scratch(pl, SCR_ROWX, max_sets * N * sizeof(double), &v))) return rc;
 	double *xr = (double *)v;
-	if ((rc = scratch(pl, SCR_J2TAB, max_tab, &v))) return rc;
-	char *tab = (char *)v;
 	const bool fuse = tspws_fused_forward(pl);
 	const bool vec = (ld % 4 == 0) && (((uintptr_t)d_x & 15) == 0);
 	const unsigned nbx = (unsigned)((N + 1023) / 1024), nb256 = (unsigned)((N + 255) / 256);
@@ -351,19 +354,17 @@ int shared_walk(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t l
 
 	for (const Round &r : rounds) {
 		const size_t ne = r.j1 - r.j0, nrep = ne * C, nsl = ne * W, nsets = nrep + (main ? 2 * ne : 0), nrows = nsl * KM;
-		const size_t q0 = T.run_ptr[r.j0 * ntile], nruns = T.run_ptr[r.j1 * ntile] - q0, f0 = T.flush_ptr[r.j0], nfl = T.flush_ptr[r.j1] - f0;
+		const size_t q0 = T.run_ptr[r.j0 * ntile], nruns = T.run_ptr[r.j1 * ntile] - q0, f0 = T.flush_ptr[r.j0];
 		stats->rounds++;
 		stats->rows += (unsigned)nrows;
-		// the round's tables in one block: trace counts (doubles) | runs | (ensemble, tile) run ranges | flush rows | counts | output rows
-		const size_t o_run = nsl * sizeof(double), o_wg = o_run + nruns * sizeof(RunDesc), o_fl = o_wg + ne * ntile * sizeof(J2Wg), o_cnt = o_fl + nfl * 4,
-		             o_row = o_cnt + nsl * 4, bytes = o_row + nsl * 4;
-		if (bytes > max_tab) return fail(TSPWS_E_ARG, "jackknife_batch_two_stage: table bound"); // (cannot happen: tab_bytes is an upper bound)
-		keep.emplace_back(bytes, 0);
-		char *blob = keep.back().data();
-		double *Mv = (double *)blob;
-		RunDesc *hr = (RunDesc *)(blob + o_run);
-		J2Wg *hw = (J2Wg *)(blob + o_wg);
-		unsigned *hfl = (unsigned *)(blob + o_fl), *hcnt = (unsigned *)(blob + o_cnt), *hrow = (unsigned *)(blob + o_row);
+		// the round's tables (here the counts are the round's own: the bound holds with equality)
+		const J2Tab o = tab_of(r.j0, r.j1);
+		if (o.bytes > max_tab) return fail(TSPWS_E_ARG, "jackknife_batch_two_stage: table bound"); // (cannot happen)
+		char *blob = call.block(o.bytes), *tab;
+		double *Mv = (double *)(blob + o.mv);
+		RunDesc *hr = (RunDesc *)(blob + o.run);
+		J2Wg *hw = (J2Wg *)(blob + o.wg);
+		unsigned *hfl = (unsigned *)(blob + o.fl), *hcnt = (unsigned *)(blob + o.cnt), *hrow = (unsigned *)(blob + o.row);
 		bool unwritten = false;
 		for (size_t j = r.j0; j < r.j1; j++) {
 			const Ens &e = T.ens[j];
@@ -384,11 +385,11 @@ int shared_walk(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t l
 			}
 		}
 		for (size_t k = 0; k < nruns; k++) { hr[k] = T.runs[q0 + k]; hr[k].frow = (unsigned)(T.runs[q0 + k].frow - f0); }
-		HIP_TRY(hipMemcpyAsync(tab, blob, bytes, hipMemcpyHostToDevice, st));
-		const double *d_Mv = (const double *)tab;
-		const RunDesc *d_runs = (const RunDesc *)(tab + o_run);
-		const J2Wg *d_wg = (const J2Wg *)(tab + o_wg);
-		const unsigned *d_fl = (const unsigned *)(tab + o_fl), *d_cnt = (const unsigned *)(tab + o_cnt), *d_row = (const unsigned *)(tab + o_row);
+		if ((rc = call.upload(pl, SCR_BTAB, blob, o.bytes, &tab, max_tab))) return rc;
+		const double *d_Mv = (const double *)(tab + o.mv);
+		const RunDesc *d_runs = (const RunDesc *)(tab + o.run);
+		const J2Wg *d_wg = (const J2Wg *)(tab + o.wg);
+		const unsigned *d_fl = (const unsigned *)(tab + o.fl), *d_cnt = (const unsigned *)(tab + o.cnt), *d_row = (const unsigned *)(tab + o.row);
 
 		// the walk: every ensemble's traces once
 		if (unwritten) HIP_TRY(hipMemsetAsync(rows, 0, nrows * N * sizeof(double), st));
@@ -420,11 +421,11 @@ int shared_walk(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t l
 // The shared walk over the ensembles list[0 .. n) of a batch (indices into h_first, ascending; every one two-stage, with traces; column
 // h_first[b] - h_first[0] of h_sel[C][Tn] is the first of ensemble b): host tables in one pass over the selection, then rounds of whole ensembles.
 // Ensemble b writes rows b * C + c of the replica outputs and of h_mtr_out and, with `main`, row b of d_ls / d_ts; stats: rounds and rows are
-// counted up.  `keep` holds the host sources of the uploads: the caller synchronises `st` before it lets them go.  (Also what
+// counted up.  The work goes to the stream of the caller's BatchCall, which also owns the uploads' host sources.  (Also what
 // tspws_hip_subsample_batch runs for its two-stage ensembles, sub_batch.hip.)
 int tspws_jb2_shared(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *h_first, const unsigned *list, size_t n, const char *h_sel,
-                     size_t Tn, unsigned C, bool main, float *d_ls, float *d_ts, float *d_ls_out, float *d_ts_out, unsigned *h_mtr_out, hipStream_t st,
-                     std::vector<std::vector<char>> &keep, tspws_hip_jk_batch2_stats *stats)
+                     size_t Tn, unsigned C, bool main, float *d_ls, float *d_ts, float *d_ls_out, float *d_ts_out, unsigned *h_mtr_out, BatchCall &call,
+                     tspws_hip_jk_batch2_stats *stats)
 {
 	const unsigned KM = p->Kmax, W = C + (main ? 1u : 0u), ntile = (W + J2_W - 1) / J2_W;
 	Tables T;
@@ -442,7 +443,7 @@ int tspws_jb2_shared(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, siz
 		T.ens.push_back(e);
 		if (T.flush.size() > 0xfffffff0ull) return fail(TSPWS_E_ARG, "jackknife_batch_two_stage: more than 2^32 partial-stack rows");
 	}
-	return shared_walk(pl, p, d_x, ld, T, C, main, ntile, d_ls, d_ts, d_ls_out, d_ts_out, h_mtr_out, st, keep, stats);
+	return shared_walk(pl, p, d_x, ld, T, C, main, ntile, d_ls, d_ts, d_ls_out, d_ts_out, h_mtr_out, call, stats);
 }
 
 extern "C" int tspws_hip_jackknife_batch_two_stage(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *h_first, unsigned B,
@@ -477,37 +478,28 @@ extern "C" int tspws_hip_jackknife_batch_two_stage(tspws_hip_plan *pl, const t_t
 	pl->jk_batch2_stats = tspws_hip_jk_batch2_stats();
 	pl->jk_batch2_stats.empty = B - (unsigned)nonempty.size();
 	pl->jk_batch2_stats.tiles = ntile;
-	std::vector<std::vector<char>> keep; // host sources of the uploads: alive until the final synchronisation
+	BatchCall call(st);
 	if (nonempty.size() == 1) {
 		// one ensemble: the single call, with its columns of the selection
 		const unsigned b = nonempty[0];
 		const size_t f = h_first[b], m = h_first[b + 1] - f;
-		std::vector<char> sel((size_t)C * m);
-		for (unsigned c = 0; c < C; c++) memcpy(sel.data() + (size_t)c * m, h_sel + (size_t)c * Tn + (f - h_first[0]), m);
+		const char *sel = ensemble_selection(call, h_sel, C, Tn, f - h_first[0], m);
 		pl->jk_batch2_stats.looped = 1;
 		float *lo = d_ls_out + (size_t)b * C * N, *to = d_ts_out + (size_t)b * C * N;
-		if (main) rc = tspws_hip_stack_jackknife(pl, p, d_x + f * ld, ld, m, d_ls + (size_t)b * N, d_ts + (size_t)b * N, sel.data(), C, lo, to, h_mtr_out + (size_t)b * C, s);
-		else rc = tspws_hip_jackknife(pl, p, d_x + f * ld, ld, m, sel.data(), C, lo, to, h_mtr_out + (size_t)b * C, s);
+		if (main) rc = tspws_hip_stack_jackknife(pl, p, d_x + f * ld, ld, m, d_ls + (size_t)b * N, d_ts + (size_t)b * N, sel, C, lo, to, h_mtr_out + (size_t)b * C, s);
+		else rc = tspws_hip_jackknife(pl, p, d_x + f * ld, ld, m, sel, C, lo, to, h_mtr_out + (size_t)b * C, s);
 		if (rc) return rc;
-		HIP_TRY(hipStreamSynchronize(st)); // (`sel` goes out of scope)
 	} else if (nonempty.size() > 1) {
 		pl->jk_batch2_stats.shared = (unsigned)nonempty.size();
-		if ((rc = tspws_jb2_shared(pl, p, d_x, ld, h_first, nonempty.data(), nonempty.size(), h_sel, Tn, C, main, d_ls, d_ts, d_ls_out, d_ts_out, h_mtr_out, st, keep,
-		                           &pl->jk_batch2_stats))) { (void)hipStreamSynchronize(st); return rc; }
+		if ((rc = tspws_jb2_shared(pl, p, d_x, ld, h_first, nonempty.data(), nonempty.size(), h_sel, Tn, C, main, d_ls, d_ts, d_ls_out, d_ts_out, h_mtr_out, call,
+		                           &pl->jk_batch2_stats))) return rc;
 	}
 	// empty ensembles: zero rows, zero counts
 	for (unsigned b = 0; b < B; b++)
-		if (h_first[b + 1] == h_first[b]) {
-			for (unsigned c = 0; c < C; c++) h_mtr_out[(size_t)b * C + c] = 0;
-			HIP_TRY(hipMemsetAsync(d_ls_out + (size_t)b * C * N, 0, (size_t)C * N * sizeof(float), st));
-			HIP_TRY(hipMemsetAsync(d_ts_out + (size_t)b * C * N, 0, (size_t)C * N * sizeof(float), st));
-			if (main) {
-				HIP_TRY(hipMemsetAsync(d_ls + (size_t)b * N, 0, N * sizeof(float), st));
-				HIP_TRY(hipMemsetAsync(d_ts + (size_t)b * N, 0, N * sizeof(float), st));
-			}
-		}
+		if (h_first[b + 1] == h_first[b]) std::fill_n(h_mtr_out + (size_t)b * C, C, 0u);
+	if ((rc = zero_empty_ensembles(h_first, B, st, {{d_ls_out, (size_t)C * N}, {d_ts_out, (size_t)C * N}, {d_ls, N}, {d_ts, N}}))) return rc;
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st)); // outputs complete; the host tables of the uploads go out of scope
+	HIP_TRY(call.drain()); // outputs complete
 	return 0;
 }
 

@@ -22,6 +22,7 @@
 // Nothing is atomic; every output has one writer and every sum a fixed order.
 #include "tspws_internal.h"
 #include "batch_kernels.h"
+#include "batch_host.h"
 
 #define is_two_stage tspws_is_two_stage
 
@@ -39,11 +40,7 @@ __global__ void __launch_bounds__(256) k_sb_accumulate(const double2 *__restrict
                                                        size_t ncoef, const SbEns *__restrict__ ens, const unsigned char *__restrict__ bits, unsigned M,
                                                        unsigned g0, double2 *__restrict__ planes)
 {
-	unsigned lo = 0, hi = S;
-	while (hi - lo > 1) {
-		const unsigned mid = (lo + hi) >> 1;
-		if (sc[mid].acc_off <= blockIdx.x) lo = mid; else hi = mid;
-	}
+	const unsigned lo = find_block_scale(sc, S, blockIdx.x, false);
 	const unsigned Ns = sc[lo].Ns, nsplit = sc[lo].nsplit;
 	const unsigned k = (blockIdx.x - sc[lo].acc_off) * 256 + threadIdx.x;
 	if (k >= Ns) return;
@@ -150,61 +147,63 @@ namespace {
 
 struct Ens { unsigned b; size_t f, m; }; // ensemble with traces: index, first trace, traces
 
+// the tables of a round in one block: ensembles | K of every row | mask bytes
+struct SbTab { size_t ens, kc, bits, bytes; };
+SbTab sb_tab(size_t ne, size_t nrows, size_t nbits)
+{
+	TableLayout lay;
+	const size_t ens = lay.add<SbEns>(ne), kc = lay.add<unsigned>(nrows), bits = lay.add<unsigned char>(nbits);
+	return {ens, kc, bits, lay.bytes};
+}
+
 // the single-stage ensembles E of the batch in rounds
 int single_rounds(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, size_t first0, const std::vector<Ens> &E, unsigned M, const char *h_sel,
-                  size_t Tn, float *d_ls_out, float *d_ts_out, const unsigned *h_Kc, hipStream_t st, std::vector<std::vector<char>> &keep)
+                  size_t Tn, float *d_ls_out, float *d_ts_out, const unsigned *h_Kc, BatchCall &call)
 {
 	const size_t N = pl->N, nc = pl->ncoef, n = E.size(), budget = tspws_part_budget_bytes();
+	hipStream_t st = call.stream();
 	const unsigned ng = (M + 7) / 8;
 	int rc;
 	void *v;
 	// rounds of whole ensembles: the partials of their traces, a plane pair per (ensemble, mask) and the tables within the budget; ensembles
 	// within grid.z, partial indices and rows within 32 bits
-	auto tab_bytes = [&](size_t ne, size_t ntr) { return ne * (sizeof(SbEns) + (size_t)M * 4) + ntr * ng + 64; };
-	struct Round { size_t j0, j1, ntr; };
-	std::vector<Round> rounds;
+	std::vector<size_t> tr0(n + 1, 0); // traces in front of ensemble j
+	for (size_t j = 0; j < n; j++) tr0[j + 1] = tr0[j] + E[j].m;
+	auto tab_of = [&](size_t j0, size_t j1) { return sb_tab(j1 - j0, (j1 - j0) * M, (tr0[j1] - tr0[j0]) * ng); };
+	const std::vector<Round> rounds = whole_ensemble_rounds(n, [&](size_t j0, size_t j1) {
+		const size_t ne = j1 - j0, nt = tr0[j1] - tr0[j0];
+		return !(ne > 65535 || ne * M > 0xfffffff0ull || nt > 0xfffffff0ull || nt * pl->npart * sizeof(double2) > budget || ne * M * 2 * nc * sizeof(double2) > budget ||
+		         tab_of(j0, j1).bytes > budget);
+	});
 	size_t max_ntr = 0, max_ne = 0, max_tab = 0;
-	for (size_t j0 = 0, j1; j0 < n; j0 = j1) {
-		size_t ntr = E[j0].m;
-		for (j1 = j0 + 1; j1 < n; j1++) {
-			const size_t ne = j1 + 1 - j0, nt = ntr + E[j1].m;
-			if (ne > 65535 || ne * M > 0xfffffff0ull || nt > 0xfffffff0ull || nt * pl->npart * sizeof(double2) > budget || ne * M * 2 * nc * sizeof(double2) > budget ||
-			    tab_bytes(ne, nt) > budget)
-				break;
-			ntr = nt;
-		}
-		rounds.push_back({j0, j1, ntr});
-		max_ntr = std::max(max_ntr, ntr);
-		max_ne = std::max(max_ne, j1 - j0);
-		max_tab = std::max(max_tab, tab_bytes(j1 - j0, ntr));
+	for (const Round &r : rounds) {
+		max_ntr = std::max(max_ntr, tr0[r.j1] - tr0[r.j0]);
+		max_ne = std::max(max_ne, r.j1 - r.j0);
+		max_tab = std::max(max_tab, tab_of(r.j0, r.j1).bytes);
 	}
 	if (max_ntr > 0xfffffff0ull || max_ne * M > 0xfffffff0ull) return fail(TSPWS_E_ARG, "subsample_batch: more than 2^32 traces or mask rows in one ensemble");
-	// rows per finish batch: even (the inverse pairs the same rows whatever the batching), sets / reconstructions / octave buffer within the budget
-	const size_t per_row = std::max({nc * sizeof(double2), N * sizeof(double), (size_t)(pl->inv_noct + 1) * N * sizeof(double)});
-	const size_t RB = std::min<size_t>({max_ne * M, 65534, std::max<size_t>(2, (budget / per_row) & ~(size_t)1)});
+	// rows per finish batch
+	const size_t RB = even_rows_per_batch(budget, tspws_inverse_row_bytes(pl), max_ne * M);
 	if ((rc = scratch(pl, SCR_PART, std::max<size_t>(2, max_ntr) * pl->npart * sizeof(double2), &v))) return rc;
 	double2 *part = (double2 *)v;
 	if ((rc = scratch(pl, SCR_SBPL, max_ne * M * 2 * nc * sizeof(double2), &v))) return rc;
 	double2 *planes = (double2 *)v;
-	if ((rc = scratch(pl, SCR_SBY, RB * nc * sizeof(double2), &v))) return rc;
+	if ((rc = scratch(pl, SCR_ROWY, RB * nc * sizeof(double2), &v))) return rc;
 	double2 *OUT = (double2 *)v;
-	if ((rc = scratch(pl, SCR_SBX, RB * N * sizeof(double), &v))) return rc;
+	if ((rc = scratch(pl, SCR_ROWX, RB * N * sizeof(double), &v))) return rc;
 	double *xr = (double *)v;
-	if ((rc = scratch(pl, SCR_SBTAB, max_tab, &v))) return rc;
-	char *tab = (char *)v;
 	const unsigned nb256 = (unsigned)((N + 255) / 256);
 
 	for (const Round &r : rounds) {
 		const size_t ne = r.j1 - r.j0, nrows = ne * M;
 		pl->sub_batch_stats.rounds++;
-		// the round's tables in one block: ensembles | K of every row | mask bytes
-		const size_t o_kc = ne * sizeof(SbEns), o_bits = o_kc + nrows * 4, bytes = o_bits + r.ntr * ng;
-		if (bytes > max_tab) return fail(TSPWS_E_ARG, "subsample_batch: table bound"); // (cannot happen: tab_bytes is an upper bound)
-		keep.emplace_back(bytes, 0);
-		char *blob = keep.back().data();
-		SbEns *he = (SbEns *)blob;
-		unsigned *hkc = (unsigned *)(blob + o_kc);
-		unsigned char *hb = (unsigned char *)(blob + o_bits);
+		// the round's tables (here the counts are the round's own: the bound holds with equality)
+		const SbTab o = tab_of(r.j0, r.j1);
+		if (o.bytes > max_tab) return fail(TSPWS_E_ARG, "subsample_batch: table bound"); // (cannot happen)
+		char *blob = call.block(o.bytes), *tab;
+		SbEns *he = (SbEns *)(blob + o.ens);
+		unsigned *hkc = (unsigned *)(blob + o.kc);
+		unsigned char *hb = (unsigned char *)(blob + o.bits);
 		size_t t = 0;
 		for (size_t j = r.j0; j < r.j1; j++) {
 			const Ens &e = E[j];
@@ -221,10 +220,10 @@ int single_rounds(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t
 			}
 			t += e.m;
 		}
-		HIP_TRY(hipMemcpyAsync(tab, blob, bytes, hipMemcpyHostToDevice, st));
-		const SbEns *d_ens = (const SbEns *)tab;
-		const unsigned *d_kc = (const unsigned *)(tab + o_kc);
-		const unsigned char *d_bits = (const unsigned char *)(tab + o_bits);
+		if ((rc = call.upload(pl, SCR_BTAB, blob, o.bytes, &tab, max_tab))) return rc;
+		const SbEns *d_ens = (const SbEns *)(tab + o.ens);
+		const unsigned *d_kc = (const unsigned *)(tab + o.kc);
+		const unsigned char *d_bits = (const unsigned char *)(tab + o.bits);
 
 		// every trace of the round once: a forward call per stretch of contiguous traces
 		for (size_t j = r.j0; j < r.j1;) {
@@ -303,12 +302,7 @@ extern "C" int tspws_hip_subsample_batch_sel(tspws_hip_plan *pl, const t_tsPWS *
 	std::vector<unsigned> two;
 	for (unsigned b = 0; b < B; b++) {
 		const size_t f = h_first[b], m = h_first[b + 1] - f;
-		for (unsigned q = 0; q < M; q++) {
-			const char *row = h_sel + (size_t)q * Tn + (f - first0);
-			unsigned k = 0;
-			for (size_t i = 0; i < m; i++) k += row[i] == 1;
-			h_mtr_out[(size_t)b * M + q] = k;
-		}
+		for (unsigned q = 0; q < M; q++) h_mtr_out[(size_t)b * M + q] = kept_count(h_sel + (size_t)q * Tn + (f - first0), m);
 		if (!m) continue;
 		if (is_two_stage(p, m)) two.push_back(b);
 		else single.push_back(Ens{b, f, m});
@@ -320,44 +314,38 @@ extern "C" int tspws_hip_subsample_batch_sel(tspws_hip_plan *pl, const t_tsPWS *
 	const size_t nonempty = single.size() + two.size();
 	stats.empty = B - (unsigned)nonempty;
 	stats.rows = (unsigned)(nonempty * M);
-	std::vector<std::vector<char>> keep; // host sources of the uploads: alive until the final synchronisation
+	BatchCall call(st);
 	// one ensemble: the single call with its columns -- which divides by a row's K = 0 and derives the K of a single-stage ensemble from
 	// subsmpl_p, so only without empty rows and, single-stage, with those K
 	bool loop = nonempty == 1;
+	const unsigned b = !loop ? 0 : two.empty() ? single[0].b : two[0];
 	if (loop) {
-		const unsigned b = two.empty() ? single[0].b : two[0];
 		const size_t K = (size_t)ceil((double)(h_first[b + 1] - h_first[b]) * p->subsmpl_p);
 		for (unsigned q = 0; q < M; q++) loop &= h_mtr_out[(size_t)b * M + q] != 0 && (!two.empty() || h_mtr_out[(size_t)b * M + q] == K);
 	}
 	if (loop) {
-		const unsigned b = two.empty() ? single[0].b : two[0];
 		const size_t f = h_first[b], m = h_first[b + 1] - f;
-		std::vector<char> sel((size_t)M * m);
-		for (unsigned q = 0; q < M; q++) memcpy(sel.data() + (size_t)q * m, h_sel + (size_t)q * Tn + (f - first0), m);
+		const char *sel = ensemble_selection(call, h_sel, M, Tn, f - first0, m);
 		stats.looped = 1;
-		if ((rc = tspws_hip_subsample_sel(pl, p, d_x + f * ld, ld, m, M, sel.data(), d_ls_out + (size_t)b * M * N, d_ts_out + (size_t)b * M * N, s))) return rc;
-		HIP_TRY(hipStreamSynchronize(st)); // (`sel` goes out of scope)
+		if ((rc = tspws_hip_subsample_sel(pl, p, d_x + f * ld, ld, m, M, sel, d_ls_out + (size_t)b * M * N, d_ts_out + (size_t)b * M * N, s))) return rc;
 	} else {
 		if (!single.empty()) {
 			stats.single_shared = (unsigned)single.size();
-			if ((rc = single_rounds(pl, p, d_x, ld, first0, single, M, h_sel, Tn, d_ls_out, d_ts_out, h_mtr_out, st, keep))) { (void)hipStreamSynchronize(st); return rc; }
+			if ((rc = single_rounds(pl, p, d_x, ld, first0, single, M, h_sel, Tn, d_ls_out, d_ts_out, h_mtr_out, call))) return rc;
 		}
 		if (!two.empty()) {
 			stats.two_stage_shared = (unsigned)two.size();
+			// (single_rounds has enqueued every round and kept no pointer: the walk may size the shared slots -- tables, sets, reconstructions -- anew)
 			tspws_hip_jk_batch2_stats walk = tspws_hip_jk_batch2_stats();
-			if ((rc = tspws_jb2_shared(pl, p, d_x, ld, h_first, two.data(), two.size(), h_sel, Tn, M, false, nullptr, nullptr, d_ls_out, d_ts_out, h_mtr_out, st, keep,
-			                           &walk))) { (void)hipStreamSynchronize(st); return rc; }
+			if ((rc = tspws_jb2_shared(pl, p, d_x, ld, h_first, two.data(), two.size(), h_sel, Tn, M, false, nullptr, nullptr, d_ls_out, d_ts_out, h_mtr_out, call,
+			                           &walk))) return rc;
 			stats.rounds += walk.rounds;
 		}
 	}
 	// empty ensembles: zero rows (their counts are zero already)
-	for (unsigned b = 0; b < B; b++)
-		if (h_first[b + 1] == h_first[b]) {
-			HIP_TRY(hipMemsetAsync(d_ls_out + (size_t)b * M * N, 0, (size_t)M * N * sizeof(float), st));
-			HIP_TRY(hipMemsetAsync(d_ts_out + (size_t)b * M * N, 0, (size_t)M * N * sizeof(float), st));
-		}
+	if ((rc = zero_empty_ensembles(h_first, B, st, {{d_ls_out, (size_t)M * N}, {d_ts_out, (size_t)M * N}}))) return rc;
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st)); // outputs complete; the host tables of the uploads go out of scope
+	HIP_TRY(call.drain()); // outputs complete
 	return 0;
 }
 

@@ -11,10 +11,11 @@
 //   spectral.hip  the far-decimated octaves through the traces' spectra (spectral.h)
 //   jk_single.hip single-stage jackknife from per-class stacks
 //   batch.hip     many same-length ensembles in one call
-//   jk_batch.hip  single-stage jackknife of many ensembles in one call (batch_kernels.h: the small kernels those three share)
+//   jk_batch.hip  single-stage jackknife of many ensembles in one call
 //   jk_batch_two_stage.hip  two-stage jackknife of many ensembles in one call
 //   conv_batch.hip  convergence curves of many ensembles in one call
 //   sub_batch.hip   random subsamples of many ensembles in one call
+//                 (batch_kernels.h: the kernels those units share; batch_host.h: their host scaffold -- upload lifetime, table layouts, rounds)
 //   comm.hip      trace shards on several devices of one process: RCCL all-reduce, sharded tspws_main driver
 //
 // Layout in HBM
@@ -178,7 +179,9 @@ struct AccExtra {
 	bool fused_done = false;          // the fused forward kernel completed (and weighted) the stacks of its scales itself: only the others are left
 };
 
-enum { SCR_Y = 0, SCR_PART, SCR_XT, SCR_OBUF, SCR_SEL, SCR_SUBST, SCR_CONV, SCR_CHUNK, SCR_P, SCR_STPS, SCR_OUT, SCR_X2, SCR_CLS, SCR_JKP, SCR_JKOUT, SCR_TAB, SCR_FZ, SCR_JKTAB, SCR_SPA, SCR_SPB, SCR_SPG, SCR_SPH, SCR_SPM, SCR_SPK, SCR_GEMM, SCR_J1TAB, SCR_J1PL, SCR_J1T, SCR_BTAB, SCR_BXG, SCR_BY, SCR_BX, SCR_BP, SCR_JBTAB, SCR_JBPL, SCR_JBT, SCR_JBY, SCR_JBX, SCR_J2TAB, SCR_J2P, SCR_J2ST, SCR_J2Y, SCR_J2X, SCR_CBTAB, SCR_CBX, SCR_CBY, SCR_CBR, SCR_CBST, SCR_CBP, SCR_CBM, SCR_SBTAB, SCR_SBPL, SCR_SBY, SCR_SBX, SCR_N };
+// (SCR_BTAB, SCR_ROWY, SCR_ROWX: the round's tables, the weighted sets of a finish batch and their reconstructions of whichever batched unit is
+// running: they never run side by side on one plan, and none keeps a pointer into these slots across a call into another unit)
+enum { SCR_Y = 0, SCR_PART, SCR_XT, SCR_OBUF, SCR_SEL, SCR_SUBST, SCR_CONV, SCR_CHUNK, SCR_P, SCR_STPS, SCR_OUT, SCR_X2, SCR_CLS, SCR_JKP, SCR_JKOUT, SCR_TAB, SCR_FZ, SCR_JKTAB, SCR_SPA, SCR_SPB, SCR_SPG, SCR_SPH, SCR_SPM, SCR_SPK, SCR_GEMM, SCR_J1TAB, SCR_J1PL, SCR_J1T, SCR_BTAB, SCR_BXG, SCR_BY, SCR_BX, SCR_BP, SCR_ROWY, SCR_ROWX, SCR_JBPL, SCR_JBT, SCR_J2P, SCR_J2ST, SCR_CBX, SCR_CBST, SCR_CBP, SCR_CBM, SCR_SBPL, SCR_N };
 
 struct OctDesc; // inverse work items (inv_poly.h)
 struct TLItem;  // many-trace forward work items (fwd_tl.h)
@@ -307,6 +310,18 @@ __device__ __forceinline__ unsigned find_scale(const ScaleDesc *sc, unsigned S, 
 	return lo;
 }
 
+// the scale that owns block `block` of an accumulate launch: the last s with acc_off[s] (k_accumulate_masked's geometry) or acc2_off[s]
+// (k_accumulate_parts') <= block
+__device__ __forceinline__ unsigned find_block_scale(const ScaleDesc *sc, unsigned S, unsigned block, bool acc2)
+{
+	unsigned lo = 0, hi = S;
+	while (hi - lo > 1) {
+		const unsigned mid = (lo + hi) >> 1;
+		if ((acc2 ? sc[mid].acc2_off : sc[mid].acc_off) <= block) lo = mid; else hi = mid;
+	}
+	return lo;
+}
+
 __device__ __forceinline__ double wave_sum(double v) // wave = 64 lanes
 {
 #pragma unroll
@@ -409,6 +424,7 @@ int  tspws_spectral_transpose(tspws_hip_plan *p, const TIn *d_x, size_t ld, unsi
 void tspws_spectral_destroy(tspws_hip_plan *p);
 // inverse.hip
 int  tspws_build_inverse(tspws_hip_plan *p);
+size_t tspws_inverse_row_bytes(const tspws_hip_plan *p); // what one row of a batched tspws_hip_inverse costs: the largest of its set, its reconstruction and its octave buffer
 int  tspws_weight_mode(double wu, int unbiased, unsigned K);
 // OUT[j] = ST[j] * weight(PS[j]) for nb stacks side by side (y_out / y_stack doubles2 apart), trace counts d_Mv[j]
 void tspws_weight_batched(tspws_hip_plan *p, double2 *OUT, const double2 *ST, const double2 *PS, int mode, double K, double wu, const double *d_Mv,
@@ -443,8 +459,9 @@ int  tspws_rows_walk_launch(const float *d_x, size_t ld, size_t N, const RunDesc
 unsigned tspws_rows_walk_wmax();
 unsigned tspws_chunk_len_for(size_t N, size_t mtr);
 // jk_batch_two_stage.hip: the shared walk over the two-stage ensembles list[0 .. n) of a batch (see there)
+class BatchCall; // (batch_host.h)
 int  tspws_jb2_shared(tspws_hip_plan *p, const t_tsPWS *par, const float *d_x, size_t ld, const size_t *h_first, const unsigned *list, size_t n,
                       const char *h_sel, size_t Tn, unsigned C, bool main, float *d_ls, float *d_ts, float *d_ls_out, float *d_ts_out, unsigned *h_mtr_out,
-                      hipStream_t st, std::vector<std::vector<char>> &keep, tspws_hip_jk_batch2_stats *stats);
+                      BatchCall &call, tspws_hip_jk_batch2_stats *stats);
 // stack.hip
 bool tspws_is_two_stage(const t_tsPWS *p, size_t mtr_global);
