@@ -400,6 +400,60 @@ typedef struct {
 } tspws_hip_sub_batch_stats;
 int  tspws_hip_subsample_batch_stats(const tspws_hip_plan *plan, tspws_hip_sub_batch_stats *stats);
 
+/* ---- bootstrap ------------------------------------------------------------------------------- */
+/* Host: one bootstrap draw of J traces with replacement, cnt[i] = how often trace i was drawn: J counts are cleared, then J draws
+ * i = (size_t)(rand() * ((double)J / ((double)RAND_MAX + 1.0))), cnt[i]++ (a draw that lands on a count of 255 is drawn again).  Returns 0;
+ * 1 for a NULL argument (nothing drawn).  J == 0 draws nothing. */
+int  tspws_bootstrap_plan(unsigned char *cnt, size_t J);
+/* Host: the counts of a batch, cnt[M][T], T = first[B] - first[0]: for b = 0 .. B-1 in order, for m = 0 .. M-1 in order,
+ * tspws_bootstrap_plan(the columns of ensemble b in row m, M_b) -- the rand() call order of a loop over the ensembles.  Empty ensembles
+ * draw nothing.  Returns 0; 1 for NULL arguments or decreasing offsets (nothing written, nothing drawn). */
+int  tspws_bootstrap_plan_batch(unsigned char *cnt, const size_t *first, unsigned B, unsigned M);
+/* M bootstrap replicas of each of B single-stage ensembles of one trace array in ONE call, the counts given.  Ensemble b = the traces
+ * [h_first[b], h_first[b+1]) of d_sigall (the rules of tspws_hip_stack_batch: B + 1 non-decreasing host offsets, h_first[0] may be > 0,
+ * ld >= max); h_cnt is [M][T] unsigned bytes, T = h_first[B] - h_first[0], column i - h_first[0] for trace i (the layout of h_sel in
+ * tspws_hip_subsample_batch_sel): cnt[m][i] = how often trace i enters replica m.  Replica (b, m) is the single-stage resampling body
+ * (tspws_subsmpl_float, :501-610) with an all-ones mask on the EXPANDED ensemble -- the traces of ensemble b in trace order, trace i
+ * repeated cnt[m][i] times -- which is never formed.  With K = K_{b,m} = the counts of row m inside ensemble b = h_mtr_out[b][m]:
+ *   ST = sum_i cnt_i Y_i, PS = sum_i cnt_i Y_i / |Y_i| (the phasor rule of the stacks), the copies added one after the other in trace order:
+ *     repeated addition, not a multiplication by the count, so the order of operations is that of the expanded ensemble, and a 0/1 count
+ *     row runs exactly the arithmetic of tspws_hip_subsample_batch_sel on that row as a mask;
+ *   tsPWS_out[b][m] = (float) Re_rec(weight(ST, PS)) with K = M = K_{b,m}, the mode chosen per row (a K = 1 row takes the K = 1 rule);
+ *   ls_out[b][m] = the FLOAT accumulator over the expanded ensemble, acc = (float)((double)acc + (double)x) once per copy in trace order
+ *     (:538-542), times (float)(1. / K_{b,m}) (:579-583).
+ * K_{b,m} = 0 gives zero rows and count 0; an empty ensemble gives zero rows and zero counts.  d_ls_out / d_ts_out are [B][M][max] floats on
+ * the device, h_mtr_out [B][M] on the host.  d_stats is NULL (not wanted) or [B][4][max] floats on the device: per sample, over the
+ * replicas of ensemble b with K > 0 (n of them), the mean of ls_out, its standard error, the mean of ts_out, its standard error -- two FP64
+ * passes in replica order over the float rows: mean = (sum v) / n, error = sqrt(sum (v - mean)^2 / (n - 1)), the bootstrap standard error;
+ * n <= 1 gives error 0, n = 0 a zero mean.  B == 0 or M == 0 returns 0 and does nothing.  NULL plan / p / h_first / h_cnt / outputs /
+ * h_mtr_out, NULL traces with T > 0, decreasing offsets, ld < max and a non-empty ensemble that is two-stage (0 < Kmax <= M_b: in the
+ * expanded ensemble a repeated trace can straddle the borders of the groups floor(k Kmax / K), which needs a walk of its own; the message
+ * says "two-stage") return TSPWS_E_ARG ("bootstrap_batch: ...") before any device work, outputs untouched; the checks that need no plan
+ * come first.  Fold and mean removal stay with the caller.
+ * In rounds of whole ensembles: the traces are transformed once (one forward launch sequence per stretch of contiguous traces), ONE
+ * segmented counted accumulation (coefficient tile x group of 8 replicas x ensemble; the 8 counts of a trace in one aligned 8-byte word)
+ * leaves every row's ST / PS planes, written once, ONE kernel forms the float-accumulator linear stacks, then the weights with each row's
+ * K, the batched inverses, the float epilogue scattered to [b][m] and ONE kernel per round for the statistics.  Nothing is atomic, every
+ * sum has a fixed order: a repeated call is bit-identical.  Every scratch block that grows with the batch stays within TSPWS_PART_MB (a
+ * round never splits an ensemble; one ensemble alone may exceed it).  The call uploads its tables and waits for `stream`: on return the
+ * outputs are complete. */
+int  tspws_hip_bootstrap_batch_cnt(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, const size_t *h_first, unsigned B,
+                                   unsigned M, const unsigned char *h_cnt, float *d_ls_out, float *d_ts_out, unsigned *h_mtr_out, float *d_stats,
+                                   void *stream);
+/* The same with the counts drawn by tspws_bootstrap_plan_batch BEFORE the call's first device call (after its refusals: a refused call
+ * draws nothing; the reason for the order stands above tspws_hip_subsample_sel).  Every K_{b,m} then is M_b. */
+int  tspws_hip_bootstrap_batch(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, const size_t *h_first, unsigned B,
+                               unsigned M, float *d_ls_out, float *d_ts_out, unsigned *h_mtr_out, float *d_stats, void *stream);
+/* How the plan's last tspws_hip_bootstrap_batch[_cnt] call with B > 0 and M > 0 went (all zero before the first one). */
+typedef struct {
+	unsigned shared;    /* ensembles that went through the segmented counted accumulation   */
+	unsigned empty;     /* ensembles without traces (zero rows, zero counts)                */
+	unsigned rounds;    /* rounds forced by the scratch budget (a round never splits an ensemble) */
+	unsigned rows;      /* replica rows finished: M per non-empty ensemble                  */
+	unsigned max_count; /* the largest count of the batch                                   */
+} tspws_hip_boot_batch_stats;
+int  tspws_hip_bootstrap_batch_stats(const tspws_hip_plan *plan, tspws_hip_boot_batch_stats *stats);
+
 /* ---- convergence curves ------------------------------------------------------------------------ */
 /* Similarity / misfit of the stack of the first i+1 traces against a reference, for i = 0..mtr-1
  * (ts_pws1f_lib.c:247-314, similarity :433-449, misfit :452-462).  d_ref_ts / d_ref_ls are [max] floats on the

@@ -144,6 +144,11 @@ SYMBOLS = {
     "tspws_hip_subsample_batch_sel": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _u, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_subsample_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _u, _vp, _vp, _vp, _vp]),
     "tspws_hip_subsample_batch_stats": (_i, [_vp, _vp]),
+    "tspws_bootstrap_plan": (_i, [_vp, _sz]),
+    "tspws_bootstrap_plan_batch": (_i, [_vp, _vp, _u, _u]),
+    "tspws_hip_bootstrap_batch_cnt": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tspws_hip_bootstrap_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _u, _vp, _vp, _vp, _vp, _vp]),
+    "tspws_hip_bootstrap_batch_stats": (_i, [_vp, _vp]),
     "tspws_hip_convergence": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence_batch_stats": (_i, [_vp, _vp]),
@@ -647,6 +652,53 @@ class Plan:
         check(self.lib.tspws_hip_subsample_batch_stats(self.h, C.byref(st)), "subsample_batch_stats")
         return dict(zip(("single_shared", "two_stage_shared", "looped", "empty", "rounds", "rows"), list(st)))
 
+    def bootstrap_batch(self, traces, first, cnt, ls_out=None, ts_out=None, mtr_out=None, stats=False):
+        """M bootstrap replicas of each of B single-stage ensembles of one trace array in ONE call (tspws_hip_bootstrap_batch_cnt): ensemble
+        b = rows [first[b], first[b+1]) of the float32 [mtr][N] device tensor `traces`; `cnt` = [M][T] uint8 counts, T = first[B] - first[0],
+        cnt[m][i - first[0]] = how often trace i enters replica m (bootstrap_counts_batch draws them).  Returns ls_out[B][M][N],
+        ts_out[B][M][N] (float32 cuda) and mtr_out[B][M] (uint32, the copies every row stacks): row [b][m] = the single-stage subsample of the
+        expanded ensemble (trace i repeated cnt[m][i] times) with every copy kept (a row without copies and an empty ensemble: zero rows,
+        count 0).  With stats=True a fourth value, float32 cuda [B][4][N]: per sample over the replicas with copies, the mean of ls_out, its
+        bootstrap standard error, the mean of ts_out, its standard error.  Two-stage ensembles (0 < Kmax <= traces) are refused.
+        Synchronises."""
+        import numpy as np
+        import torch
+        mtr, ld = self._traces(traces)
+        f = np.asarray(first)
+        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
+            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
+        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
+            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
+        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
+        B, T = f.size - 1, int(f[-1] - f[0])
+        if not isinstance(cnt, np.ndarray) or cnt.ndim != 2 or cnt.dtype != np.uint8:
+            raise TspwsError("counts must be a 2-D uint8 numpy array [M][T]")
+        if cnt.shape[1] != T:
+            raise TspwsError(f"counts must be [M][{T}] (replica x trace of the batch), got {cnt.shape}")
+        cnt = np.ascontiguousarray(cnt)
+        Mn = cnt.shape[0]
+        dev = traces.device
+        ls_out = torch.empty((B, Mn, self.N), dtype=torch.float32, device=dev) if ls_out is None else ls_out
+        ts_out = torch.empty((B, Mn, self.N), dtype=torch.float32, device=dev) if ts_out is None else ts_out
+        mtr_out = np.zeros((B, Mn), np.uint32) if mtr_out is None else mtr_out
+        if not isinstance(mtr_out, np.ndarray) or mtr_out.dtype != np.uint32 or mtr_out.shape != (B, Mn) or not mtr_out.flags.c_contiguous:
+            raise TspwsError(f"mtr_out must be a contiguous uint32 numpy array [{B}][{Mn}]")
+        for t, name in ((ls_out, "ls_out"), (ts_out, "ts_out")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (B, Mn, self.N) or not t.is_contiguous() or \
+                    not t.is_cuda or (t.device.index or 0) != self.device:
+                raise TspwsError(f"{name} must be a contiguous float32 [{B}][{Mn}][{self.N}] tensor on cuda:{self.device}")
+        st = torch.empty((B, 4, self.N), dtype=torch.float32, device=dev) if stats else None
+        check(self.lib.tspws_hip_bootstrap_batch_cnt(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, Mn, cnt.ctypes.data,
+                                                     ls_out.data_ptr(), ts_out.data_ptr(), mtr_out.ctypes.data, st.data_ptr() if stats else None,
+                                                     self._stream()), "bootstrap_batch_cnt")
+        return (ls_out, ts_out, mtr_out, st) if stats else (ls_out, ts_out, mtr_out)
+
+    def bootstrap_batch_stats(self):
+        """How the last bootstrap_batch call with B > 0 and M > 0 went (tspws_hip_bootstrap_batch_stats): dict of counts."""
+        st = (C.c_uint * 5)()
+        check(self.lib.tspws_hip_bootstrap_batch_stats(self.h, C.byref(st)), "bootstrap_batch_stats")
+        return dict(zip(("shared", "empty", "rounds", "rows", "max_count"), list(st)))
+
     def _refs(self, t, name, rows):
         """Data pointer of a reference array: contiguous float32 [rows][N] (or [N] for one row) on the plan's device."""
         import torch
@@ -969,6 +1021,21 @@ def subsampling_selection_batch(first, M, prob):
     if load().tspws_subsampling_plan_batch(sel.ctypes.data, f.ctypes.data, f.size - 1, int(M), float(prob)):
         raise TspwsError("tspws_subsampling_plan_batch refused its arguments")
     return sel
+
+
+def bootstrap_counts_batch(first, M):
+    """Bootstrap counts of a batch (tspws_bootstrap_plan_batch): uint8 [M][T], T = first[-1] - first[0]; for every ensemble in order and every
+    replica in order, M_b draws with replacement among the ensemble's columns of that row (its counts sum to M_b), drawn with libc rand()
+    in the order of a loop over the ensembles."""
+    import numpy as np
+    f = np.asarray(first)
+    if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu" or (f < 0).any() or (np.diff(f) < 0).any():
+        raise TspwsError("first must be a 1-D array of B + 1 non-decreasing, non-negative integer offsets")
+    f = np.ascontiguousarray(f, dtype=np.uint64)
+    cnt = np.zeros((int(M), int(f[-1] - f[0])), np.uint8)
+    if load().tspws_bootstrap_plan_batch(cnt.ctypes.data, f.ctypes.data, f.size - 1, int(M)):
+        raise TspwsError("tspws_bootstrap_plan_batch refused its arguments")
+    return cnt
 
 
 def selection_classes(sel):

@@ -1,5 +1,6 @@
 // batch_kernels.h -- small kernels that the batched entry points share: the gather of batch.hip and jk_batch.hip, the class time sums and the
-// replicas' finish (weighted sets, linear stacks) of jk_single.hip and jk_batch.hip, the per-row weight mode of those and sub_batch.hip.  Every
+// replicas' finish (weighted sets, linear stacks) of jk_single.hip and jk_batch.hip, the per-row weight mode of those and sub_batch.hip, the
+// rows' finish (weighted sets, float epilogue) of sub_batch.hip and boot_batch.hip.  Every
 // unit that includes this header gets its own copy (internal linkage: the units are compiled without relocatable device code).
 #pragma once
 
@@ -102,4 +103,34 @@ template <bool LDS>
 	double acc = 0;
 	for (unsigned k = 0; k < e.ncls; k++) if (kr[k]) acc += T[(size_t)(e.cls0 + k) * N + n];
 	out[((size_t)e.row * C + c) * N + n] = K ? (float)(acc * (1.0 / (double)K)) : 0.f;
+}
+
+// A single-stage ensemble of a round of sub_batch.hip / boot_batch.hip: first trace, its selection table, traces, index of its first trace in
+// the round's partials, output block.  The table of group g of 8 rows holds one entry per trace j at [bits_off + g m + j]: sub_batch.hip a
+// byte with the 8 mask bits, boot_batch.hip an aligned 8-byte word with the 8 count bytes.
+struct SbEns { unsigned long long t0, bits_off; unsigned m, part0, row, pad; };
+
+// weighted coefficients of the rows r0 + blockIdx.y of the round: OUT = ST * weight(PS; K = M = K_r), the mode by the row's own K (K = 1: the
+// K = 1 rule, ts_pws1f_lib.c:972); K = 0: a zero set
+[[maybe_unused]] static __global__ void __launch_bounds__(256) k_sb_weight(double2 *__restrict__ OUT, const double2 *__restrict__ planes, size_t ncoef,
+                                                                            const unsigned *__restrict__ Kc, size_t r0, double wu, int unbiased)
+{
+	const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= ncoef) return;
+	const size_t r = r0 + blockIdx.y;
+	const unsigned K = Kc[r];
+	double2 o = make_double2(0, 0);
+	if (K) o = weight_value(planes[r * 2 * ncoef + i], planes[r * 2 * ncoef + ncoef + i], j1_weight_mode(wu, unbiased, K), (double)K, (double)K, wu);
+	OUT[(size_t)blockIdx.y * ncoef + i] = o;
+}
+
+// tsPWS_out of the rows r0 + blockIdx.y of the round (row r = mask r % M of the round's ensemble r / M): (float) x to block [b][m]; K = 0: zero
+[[maybe_unused]] static __global__ void __launch_bounds__(256) k_sb_epilogue(const double *__restrict__ x, size_t N, const SbEns *__restrict__ ens,
+                                                                              const unsigned *__restrict__ Kc, unsigned M, size_t r0, float *__restrict__ ts_out)
+{
+	const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (n >= N) return;
+	const size_t r = r0 + blockIdx.y;
+	const unsigned q = (unsigned)(r % M);
+	ts_out[((size_t)ens[r / M].row * M + q) * N + n] = Kc[r] ? (float)x[(size_t)blockIdx.y * N + n] : 0.f;
 }

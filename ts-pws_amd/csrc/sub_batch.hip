@@ -26,13 +26,8 @@
 
 #define is_two_stage tspws_is_two_stage
 
-namespace {
-
-// a single-stage ensemble of a round: first trace, its mask bytes (group g of 8 masks: bits[bits_off + g m + j] for trace j), traces, index of
-// its first trace in the round's partials, output block
-struct SbEns { unsigned long long t0, bits_off; unsigned m, part0, row, pad; };
-
-} // namespace
+// (SbEns, the descriptor of a single-stage ensemble of a round, and the rows' finish -- k_sb_weight, k_sb_epilogue -- are in batch_kernels.h:
+// boot_batch.hip runs them too)
 
 // ST / PS planes of the masks 8 g .. 8 g + 7 (g = g0 + blockIdx.y) of ensemble blockIdx.z of the round, one thread per coefficient (the
 // geometry of k_accumulate_masked: 256-coefficient blocks by acc_off).  Row r = blockIdx.z M + mask: planes[r][ST | PS], 2 ncoef apart.
@@ -116,31 +111,6 @@ __global__ void __launch_bounds__(256) k_sb_linear(const float *__restrict__ x, 
 			if (on[j]) acc = (float)((double)acc + (double)v[j]);
 	}
 	o[n] = acc * (float)(1. / (double)K);
-}
-
-// weighted coefficients of the rows r0 + blockIdx.y of the round: OUT = ST * weight(PS; K = M = K_r), the mode by the row's own K (K = 1: the
-// K = 1 rule, ts_pws1f_lib.c:972); K = 0: a zero set
-__global__ void __launch_bounds__(256) k_sb_weight(double2 *__restrict__ OUT, const double2 *__restrict__ planes, size_t ncoef, const unsigned *__restrict__ Kc,
-                                                   size_t r0, double wu, int unbiased)
-{
-	const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-	if (i >= ncoef) return;
-	const size_t r = r0 + blockIdx.y;
-	const unsigned K = Kc[r];
-	double2 o = make_double2(0, 0);
-	if (K) o = weight_value(planes[r * 2 * ncoef + i], planes[r * 2 * ncoef + ncoef + i], j1_weight_mode(wu, unbiased, K), (double)K, (double)K, wu);
-	OUT[(size_t)blockIdx.y * ncoef + i] = o;
-}
-
-// tsPWS_out of the rows r0 + blockIdx.y of the round (row r = mask r % M of the round's ensemble r / M): (float) x to block [b][m]; K = 0: zero
-__global__ void __launch_bounds__(256) k_sb_epilogue(const double *__restrict__ x, size_t N, const SbEns *__restrict__ ens, const unsigned *__restrict__ Kc,
-                                                     unsigned M, size_t r0, float *__restrict__ ts_out)
-{
-	const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
-	if (n >= N) return;
-	const size_t r = r0 + blockIdx.y;
-	const unsigned q = (unsigned)(r % M);
-	ts_out[((size_t)ens[r / M].row * M + q) * N + n] = Kc[r] ? (float)x[(size_t)blockIdx.y * N + n] : 0.f;
 }
 
 namespace {

@@ -15,6 +15,7 @@
 //   jk_batch_two_stage.hip  two-stage jackknife of many ensembles in one call
 //   conv_batch.hip  convergence curves of many ensembles in one call
 //   sub_batch.hip   random subsamples of many ensembles in one call
+//   boot_batch.hip  bootstrap replicas of many ensembles in one call
 //                 (batch_kernels.h: the kernels those units share; batch_host.h: their host scaffold -- upload lifetime, table layouts, rounds)
 //   comm.hip      trace shards on several devices of one process: RCCL all-reduce, sharded tspws_main driver
 //
@@ -284,6 +285,7 @@ struct tspws_hip_plan {
 	tspws_hip_jk_batch2_stats jk_batch2_stats{}; // ... and the last batched two-stage jackknife (jk_batch_two_stage.hip)
 	tspws_hip_conv_batch_stats conv_batch_stats{}; // ... and the last batched convergence curves (conv_batch.hip)
 	tspws_hip_sub_batch_stats sub_batch_stats{}; // ... and the last batched random subsampling (sub_batch.hip)
+	tspws_hip_boot_batch_stats boot_batch_stats{}; // ... and the last batched bootstrap (boot_batch.hip)
 };
 
 int tspws_scratch(tspws_hip_plan *p, int slot, size_t bytes, void **out);
