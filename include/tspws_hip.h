@@ -454,6 +454,38 @@ typedef struct {
 } tspws_hip_boot_batch_stats;
 int  tspws_hip_bootstrap_batch_stats(const tspws_hip_plan *plan, tspws_hip_boot_batch_stats *stats);
 
+/* ---- percentile bands of replicas ---------------------------------------------------------------- */
+/* Per sample, Q quantiles over the replicas of each of B ensembles.  d_rows is [B][M][ld] floats on the plan's device (what the batched
+ * resampling calls write as d_ls_out / d_ts_out: ld = max), h_mtr NULL or [B][M] host counts (their h_mtr_out): replica (b, m) takes part
+ * iff h_mtr == NULL or h_mtr[b][m] > 0.  d_bands is [B][Q][N] floats, N = the plan's trace length.
+ * For ensemble b let n be the replicas that take part and x_(0) <= ... <= x_(n-1) their values at sample s, in the order of the usual
+ * order-preserving integer key of a float's bits (negative values: all bits flipped, the others: the sign bit set; infinities sort at the
+ * ends, NaNs by their bit pattern -- inputs are meant to be finite, others neither fault nor hang and follow the same arithmetic).  For
+ * the probability q = h_q[k]: h = (double)(n - 1) * q, j = floor(h), g = h - j, and
+ *   d_bands[b][k][s] = (float) x_(j)                                                        when g == 0,
+ *                      (float)((double)x_(j) + g * ((double)x_(j+1) - (double)x_(j)))        otherwise,
+ * every FP64 operation rounded on its own: the "linear" (type 7) quantile, what numpy computes from a sort in the same IEEE operations.
+ * n = 0 gives zero bands, n = 1 that replica's row for every q.  B == 0, M == 0 or Q == 0 returns 0 and does nothing.  A NULL plan,
+ * d_rows, h_q or d_bands, ld < max, Q > 8 and a q that is NaN or outside [0, 1] return TSPWS_E_ARG ("replica_bands: ...") before any device
+ * work, outputs untouched; the checks that need no plan come first.
+ * One workgroup owns (ensemble, tile of 64 samples): M <= lds_max_rows stages the participating rows of its tile in LDS as keys (read
+ * from HBM once) and selects per lane, bit by bit; a larger M runs the same selection on columns read from global memory.  The route
+ * depends on M alone.  In rounds of whole ensembles (at most 65535 a round; the rows a round reads and its tables within TSPWS_PART_MB,
+ * one ensemble alone may exceed it); per round one small table (the participating rows of every ensemble, j and g of every (ensemble, q))
+ * is uploaded into a scratch slot of the unit's own.  Columns max .. ld-1 of d_rows are never read, nothing outside [B][Q][max] of d_bands
+ * is written, nothing is atomic: a repeated call is bit-identical.  The call waits for `stream`: on return the bands are complete. */
+int  tspws_hip_replica_bands(tspws_hip_plan *plan, const float *d_rows, size_t ld, unsigned B, unsigned M, const unsigned *h_mtr,
+                             const double *h_q, unsigned Q, float *d_bands, void *stream);
+/* How the plan's last tspws_hip_replica_bands call with B, M, Q > 0 went (zero before the first one; lds_max_rows is always set). */
+typedef struct {
+	unsigned lds;          /* ensembles selected from keys staged in LDS (M <= lds_max_rows)  */
+	unsigned global;       /* ensembles selected from columns in global memory (M above that) */
+	unsigned empty;        /* ensembles without a participating replica (zero bands)          */
+	unsigned rounds;       /* rounds of whole ensembles                                       */
+	unsigned lds_max_rows; /* the largest M that takes the LDS route                          */
+} tspws_hip_bands_stats;
+int  tspws_hip_replica_bands_stats(const tspws_hip_plan *plan, tspws_hip_bands_stats *stats);
+
 /* ---- convergence curves ------------------------------------------------------------------------ */
 /* Similarity / misfit of the stack of the first i+1 traces against a reference, for i = 0..mtr-1
  * (ts_pws1f_lib.c:247-314, similarity :433-449, misfit :452-462).  d_ref_ts / d_ref_ls are [max] floats on the

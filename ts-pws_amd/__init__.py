@@ -149,6 +149,8 @@ SYMBOLS = {
     "tspws_hip_bootstrap_batch_cnt": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_bootstrap_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _u, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_bootstrap_batch_stats": (_i, [_vp, _vp]),
+    "tspws_hip_replica_bands": (_i, [_vp, _vp, _sz, _u, _u, _vp, _vp, _u, _vp, _vp]),
+    "tspws_hip_replica_bands_stats": (_i, [_vp, _vp]),
     "tspws_hip_convergence": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence_batch_stats": (_i, [_vp, _vp]),
@@ -698,6 +700,53 @@ class Plan:
         st = (C.c_uint * 5)()
         check(self.lib.tspws_hip_bootstrap_batch_stats(self.h, C.byref(st)), "bootstrap_batch_stats")
         return dict(zip(("shared", "empty", "rounds", "rows", "max_count"), list(st)))
+
+    def replica_bands(self, rows, q, mtr=None, out=None):
+        """Per sample, the quantiles `q` (a sequence of at most 8 probabilities in [0, 1]) over the replicas of each of B ensembles
+        (tspws_hip_replica_bands): `rows` = float32 cuda [B][M][N] replica rows (ls_out / ts_out of the batched resampling calls), contiguous
+        or with a row stride through a [B][M][ld] base; `mtr` = None or their uint32 [B][M] counts (mtr_out): replica (b, m) takes part iff
+        mtr is None or mtr[b][m] > 0.  Returns float32 cuda [B][Q][N] (given as `out` or new): the "linear" quantile of the participating
+        replicas, computed in FP64 from the exact order statistics; no participating replica gives zero bands.  Synchronises."""
+        import numpy as np
+        import torch
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[2] != self.N:
+            raise TspwsError(f"rows must be a float32 [B][M][{self.N}] tensor, got {getattr(rows, 'dtype', type(rows))} {tuple(getattr(rows, 'shape', ()))}")
+        if not rows.is_cuda or (rows.device.index or 0) != self.device:
+            raise TspwsError(f"rows live on {rows.device}, the plan on cuda:{self.device}")
+        B, Mn = rows.shape[0], rows.shape[1]
+        ld = rows.stride(1) if Mn > 1 else (rows.stride(0) if B > 1 else self.N)
+        if B and Mn:
+            if rows.stride(2) != 1:
+                raise TspwsError("rows must be contiguous along the samples (stride(2) == 1)")
+            if ld < self.N:
+                raise TspwsError("overlapping replica rows (row stride < N)")
+            if B > 1 and rows.stride(0) != Mn * ld:
+                raise TspwsError("rows must be a [B][M][N] view of one [B][M][ld] base (stride(0) == M * stride(1))")
+        try:
+            qa = np.ascontiguousarray(np.asarray(q, dtype=np.float64))
+        except (TypeError, ValueError):
+            raise TspwsError("q must be a sequence of floats") from None
+        if qa.ndim != 1:
+            raise TspwsError("q must be a sequence of floats")
+        Q = qa.size
+        if mtr is not None:
+            if not isinstance(mtr, np.ndarray) or mtr.dtype != np.uint32 or mtr.shape != (B, Mn):
+                raise TspwsError(f"mtr must be None or a uint32 numpy array [{B}][{Mn}]")
+            mtr = np.ascontiguousarray(mtr)
+        out = torch.empty((B, Q, self.N), dtype=torch.float32, device=rows.device) if out is None else out
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B, Q, self.N) or not out.is_contiguous() or \
+                not out.is_cuda or (out.device.index or 0) != self.device:
+            raise TspwsError(f"out must be a contiguous float32 [{B}][{Q}][{self.N}] tensor on cuda:{self.device}")
+        check(self.lib.tspws_hip_replica_bands(self.h, rows.data_ptr(), ld, B, Mn, mtr.ctypes.data if mtr is not None else None, qa.ctypes.data, Q,
+                                               out.data_ptr(), self._stream()), "replica_bands")
+        return out
+
+    def replica_bands_stats(self):
+        """How the last replica_bands call with B, M, Q > 0 went (tspws_hip_replica_bands_stats): dict of counts; lds_max_rows = the largest
+        M whose replicas are selected from LDS."""
+        st = (C.c_uint * 5)()
+        check(self.lib.tspws_hip_replica_bands_stats(self.h, C.byref(st)), "replica_bands_stats")
+        return dict(zip(("lds", "global", "empty", "rounds", "lds_max_rows"), list(st)))
 
     def _refs(self, t, name, rows):
         """Data pointer of a reference array: contiguous float32 [rows][N] (or [N] for one row) on the plan's device."""
