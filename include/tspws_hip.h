@@ -486,6 +486,71 @@ typedef struct {
 } tspws_hip_bands_stats;
 int  tspws_hip_replica_bands_stats(const tspws_hip_plan *plan, tspws_hip_bands_stats *stats);
 
+/* ---- trace scores and the selective stack ---- */
+/* Which traces belong in the stack: the reference's two figures of merit (similarity, ts_pws1f_lib.c:433-449; misfit, :452-462) of every
+ * TRACE of B ensembles against R reference rows per ensemble, in one pass that reads every trace sample of the lag window once.  Ensemble
+ * b = the traces [h_first[b], h_first[b+1]) of d_sigall (the rules of tspws_hip_stack_batch: B + 1 non-decreasing host offsets, h_first[0]
+ * may be > 0, ld >= max), T = h_first[B] - h_first[0].  d_ref is [B][R][ldr] floats on the plan's device, 1 <= R <= 4, ldr >= max: row
+ * (b, k) is reference k of ensemble b (R = 2 with the ls and tsPWS rows of tspws_hip_stack_batch scores against both at once).  The lag
+ * window is the samples n0 <= n < n1, n0 < n1 <= max; n1 == 0 means max.  d_scores is [R][3][T] doubles on the device, the planes sim,
+ * misfit, dot, column i - h_first[0] for trace i; d_energy is NULL or [T] doubles.  For trace x of ensemble b and r = row (b, k), every sum
+ * over the window in FP64:
+ *   dot = sum (double)x[n] (double)r[n], xx = sum (double)x[n]^2, rr = sum (double)r[n]^2, misfit = sum ((double)x[n] - (double)r[n])^2,
+ *   sim = dot / sqrt(xx) / sqrt(rr) (the reference's similarity with the trace as x1), d_energy[i] = xx.
+ * A trace or a reference without energy gives the reference's NaN for sim (0 / 0) -- NaN fails every >=, so a dead trace is never
+ * selected; misfit, dot and the energy stay finite.  The order of every sum is fixed (nothing is atomic): a repeated call is bit-identical,
+ * and the scores of a trace depend only on that trace, its reference rows, the window and the load route -- a batch and a loop of
+ * one-ensemble calls on the same route give bit-equal columns, plane k of an R-reference call is that of the R = 1 call on reference k.
+ * The route: 16-byte non-temporal loads iff max % 4 == 0, ld % 4 == 0, ldr % 4 == 0 and both bases are 16-byte aligned, scalar loads
+ * otherwise; a window edge that is no multiple of 4 is a scalar head / tail.  Columns max .. ld-1 / ldr-1 are never read, nothing outside
+ * the two outputs is written.  Two levels: one wave per (up to 4 consecutive traces of an ensemble, column segment of 4096 samples) leaves
+ * partial sums in a scratch block that stays within TSPWS_PART_MB (rounds of whole ensembles; one ensemble alone may exceed it), a small
+ * kernel adds the segments in segment order.  B == 0 or T == 0 returns 0 and does nothing; an empty ensemble has no columns.  NULL plan /
+ * h_first / d_ref / d_scores, NULL traces with T > 0, decreasing offsets, ld < max, ldr < max, R == 0, R > 4, n0 >= n1 (after the n1 == 0
+ * rule) and n1 > max return TSPWS_E_ARG ("trace_scores: ...") before any device work, outputs untouched; the checks that need no plan come
+ * first.  So does a round that would need more than 2^33 waves (groups of 4 traces x column segments: one ensemble of 2^26 traces of
+ * 2^21 samples).  The call uploads one small table per round and waits for `stream`: on return the outputs are complete. */
+int  tspws_hip_trace_scores(tspws_hip_plan *plan, const float *d_sigall, size_t ld, const size_t *h_first, unsigned B, const float *d_ref,
+                            size_t ldr, unsigned R, size_t n0, size_t n1, double *d_scores, double *d_energy, void *stream);
+/* How the plan's last tspws_hip_trace_scores call with T > 0 went (all zero before the first one).  The figures are set when the call has
+ * passed its refusals, before its device work: a call that then fails in the runtime leaves the figures of its plan.  The calls that
+ * tspws_hip_selective_stack_batch makes count: after it the figures are those of its last scoring pass. */
+typedef struct {
+	unsigned vec;      /* 1: the 16-byte vector route, 0: the scalar route                 */
+	unsigned segments; /* column segments per trace                                        */
+	unsigned rounds;   /* rounds of whole ensembles                                        */
+	unsigned empty;    /* ensembles without traces                                         */
+} tspws_hip_trace_scores_stats_t;
+int  tspws_hip_trace_scores_stats(const tspws_hip_plan *plan, tspws_hip_trace_scores_stats_t *stats);
+/* Host: one mask row from one plane of scores.  score is [T] doubles (usually sim of one reference), T = first[B] - first[0]; sel receives
+ * [T] bytes (1 = kept: one row of h_sel with M = 1), kept is NULL or receives the [B] kept counts.
+ *   rule 0: keep iff score >= a.
+ *   rule 1: per ensemble over its FINITE scores, med = the median (an even count: 0.5 * (lo + hi) of the two middle order statistics),
+ *           mad = the median of fabs(score - med) by the same rule; keep iff score >= med - a * 1.4826 * mad, evaluated left to right in FP64.
+ * NaN is never kept; an ensemble without a finite score keeps nothing.  Returns 0; 1 for NULL sel / score / first or decreasing offsets
+ * (nothing written); 2 for an unknown rule or a NaN a (nothing written). */
+int  tspws_selection_from_scores(char *sel, unsigned *kept, const double *score, const size_t *first, unsigned B, int rule, double a);
+/* The selective stack of B ensembles: stack, score, select, restack, built from tspws_hip_stack_batch, tspws_hip_trace_scores (R = 1),
+ * tspws_selection_from_scores (on the sim plane) and tspws_hip_subsample_batch_sel (M = 1); no kernel of its own.  against: 0 scores
+ * against the ls row, 1 against the tsPWS row; rule / a as in tspws_selection_from_scores; n0 / n1 the lag window of the scores; iters >= 1.
+ * Pass 0: the plain stacks give the rows, every trace is scored against the chosen one, the mask is selected and the ensembles are
+ * restacked with it into d_ls / d_tsPWS ([B][max]) and h_kept ([B]).  Every further pass scores ALL traces against the rows the previous
+ * pass wrote and selects again: an unchanged mask ends the call, otherwise the ensembles are restacked.  *iters_done (NULL: not wanted) =
+ * the number of restacks, h_sel[T] = the last mask used: the final rows are, bit for bit, what tspws_hip_subsample_batch_sel(M = 1, h_sel)
+ * writes, with its definitions -- ls is that call's time-domain row (not the frame-filtered ls of tspws_hip_stack), an ensemble is
+ * two-stage by M_b (not by the kept count), an ensemble that keeps nothing gives zero rows and count 0.  NULL plan / p / h_first / outputs
+ * / h_sel / h_kept, NULL traces with T > 0, decreasing offsets, ld < max, against outside {0, 1}, an unknown rule, a NaN a, iters == 0
+ * and a bad window return TSPWS_E_ARG ("selective_stack_batch: ...") before any device work, outputs untouched; the checks that need no
+ * plan come first; an ensemble of more than 2^32 - 16 traces is refused there too (the limit of tspws_hip_subsample_batch_sel, checked
+ * up front so that no stack is computed first).  What only a composed call can judge -- a parameter set that tspws_hip_stack_batch
+ * rejects, a failed allocation, a runtime error -- returns that call's code with that call's error text ("stack_batch: ...",
+ * "subsample_batch: ...", "trace_scores: ..."), possibly after earlier passes have written the outputs.  The call overwrites the plan's
+ * stack_batch, trace_scores and subsample_batch statistics.  B == 0 returns 0 and does nothing.  Fold and mean removal stay with the
+ * caller.  Every composed call waits for `stream`: on return the outputs are complete. */
+int  tspws_hip_selective_stack_batch(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, const size_t *h_first, unsigned B,
+                                     int against, int rule, double a, unsigned iters, size_t n0, size_t n1, float *d_ls, float *d_tsPWS,
+                                     char *h_sel, unsigned *h_kept, unsigned *iters_done, void *stream);
+
 /* ---- convergence curves ------------------------------------------------------------------------ */
 /* Similarity / misfit of the stack of the first i+1 traces against a reference, for i = 0..mtr-1
  * (ts_pws1f_lib.c:247-314, similarity :433-449, misfit :452-462).  d_ref_ts / d_ref_ls are [max] floats on the

@@ -151,6 +151,10 @@ SYMBOLS = {
     "tspws_hip_bootstrap_batch_stats": (_i, [_vp, _vp]),
     "tspws_hip_replica_bands": (_i, [_vp, _vp, _sz, _u, _u, _vp, _vp, _u, _vp, _vp]),
     "tspws_hip_replica_bands_stats": (_i, [_vp, _vp]),
+    "tspws_hip_trace_scores": (_i, [_vp, _vp, _sz, _vp, _u, _vp, _sz, _u, _sz, _sz, _vp, _vp, _vp]),
+    "tspws_hip_trace_scores_stats": (_i, [_vp, _vp]),
+    "tspws_selection_from_scores": (_i, [_vp, _vp, _vp, _vp, _u, _i, _d]),
+    "tspws_hip_selective_stack_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _i, _i, _d, _u, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence_batch_stats": (_i, [_vp, _vp]),
@@ -748,6 +752,92 @@ class Plan:
         check(self.lib.tspws_hip_replica_bands_stats(self.h, C.byref(st)), "replica_bands_stats")
         return dict(zip(("lds", "global", "empty", "rounds", "lds_max_rows"), list(st)))
 
+    def _first(self, first, mtr):
+        """(first as contiguous uint64, B, T) of B + 1 ensemble offsets into `mtr` trace rows."""
+        import numpy as np
+        f = np.asarray(first)
+        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
+            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
+        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
+            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
+        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
+        return f, f.size - 1, int(f[-1] - f[0])
+
+    def _window(self, window):
+        """(n0, n1) of a lag window: None = the whole trace, else n0 <= n < n1 (n1 == 0: the trace length)."""
+        if window is None:
+            return 0, 0
+        n0, n1 = (int(v) for v in window)
+        if n0 < 0 or n1 < 0:
+            raise TspwsError("window must be (n0, n1) with 0 <= n0 < n1 <= N")
+        return n0, n1
+
+    def trace_scores(self, traces, first, refs, window=None, energy=False):
+        """Similarity, misfit and dot product of every trace of B ensembles against the reference rows of its ensemble
+        (tspws_hip_trace_scores): ensemble b = rows [first[b], first[b+1]) of the float32 [mtr][N] device tensor `traces`; `refs` = float32
+        cuda [B][R][N] (1 <= R <= 4) or [B][N] (R = 1), contiguous or a [:, :, :N] view of a wider base; `window` = None or (n0, n1), the
+        samples n0 <= n < n1 every sum runs over.  Returns a float64 cuda tensor [R][3][T] -- planes sim, misfit, dot; T = first[B] - first[0],
+        column i - first[0] for trace i; sim is NaN for a trace or a reference without energy -- and with energy=True also the traces'
+        energies, float64 cuda [T].  The outputs hold NaN before the call (an unwritten entry shows).  Synchronises."""
+        import torch
+        mtr, ld = self._traces(traces)
+        f, B, T = self._first(first, mtr)
+        if not isinstance(refs, torch.Tensor) or refs.dtype != torch.float32 or refs.dim() not in (2, 3) or refs.shape[-1] != self.N or refs.shape[0] != B:
+            raise TspwsError(f"refs must be a float32 [{B}][R][{self.N}] or [{B}][{self.N}] tensor, got {getattr(refs, 'dtype', type(refs))} "
+                             f"{tuple(getattr(refs, 'shape', ()))}")
+        if not refs.is_cuda or (refs.device.index or 0) != self.device:
+            raise TspwsError(f"refs live on {refs.device}, the plan on cuda:{self.device}")
+        if refs.dim() == 2:
+            refs = refs.unsqueeze(1)
+        R = refs.shape[1]
+        if not 1 <= R <= 4:
+            raise TspwsError(f"1 to 4 reference rows per ensemble, got {R}")
+        ldr = refs.stride(1) if R > 1 else (refs.stride(0) if B > 1 else self.N)
+        if B:
+            if refs.stride(2) != 1:
+                raise TspwsError("refs must be contiguous along the samples (stride(2) == 1)")
+            if ldr < self.N:
+                raise TspwsError("overlapping reference rows (row stride < N)")
+            if B > 1 and refs.stride(0) != R * ldr:
+                raise TspwsError("refs must be a [B][R][N] view of one [B][R][ld] base (stride(0) == R * stride(1))")
+        n0, n1 = self._window(window)
+        scores = torch.full((R, 3, T), float("nan"), dtype=torch.float64, device=traces.device)
+        en = torch.full((T,), float("nan"), dtype=torch.float64, device=traces.device) if energy else None
+        if not T:  # no columns: nothing to call with (an empty tensor has no address)
+            return (scores, en) if energy else scores
+        check(self.lib.tspws_hip_trace_scores(self.h, traces.data_ptr(), ld, f.ctypes.data, B, refs.data_ptr(), ldr, R, n0, n1, scores.data_ptr(),
+                                              en.data_ptr() if energy else None, self._stream()), "trace_scores")
+        return (scores, en) if energy else scores
+
+    def trace_scores_stats(self):
+        """How the last trace_scores call with traces went (tspws_hip_trace_scores_stats): dict(vec, segments, rounds, empty)."""
+        st = (C.c_uint * 4)()
+        check(self.lib.tspws_hip_trace_scores_stats(self.h, C.byref(st)), "trace_scores_stats")
+        return dict(zip(("vec", "segments", "rounds", "empty"), list(st)))
+
+    def selective_stack_batch(self, traces, first, against="ts", rule="mad", a=3.0, iters=2, window=None):
+        """The selective stack of B ensembles (tspws_hip_selective_stack_batch): stack, score every trace against the ensemble's own
+        `against` row ("ls" or "ts"), keep by `rule` ("threshold": sim >= a; "mad": sim >= median - a * 1.4826 * MAD of the ensemble's finite
+        scores), restack; up to `iters` restacks, ending early when the mask no longer changes.  Returns (ls[B][N], ts[B][N]) float32 cuda --
+        bit for bit the rows of subsample_batch(traces, first, sel[None]) --, sel int8 [T] (the last mask used), kept uint32 [B] and the
+        number of restacks.  Synchronises."""
+        import numpy as np
+        import torch
+        mtr, ld = self._traces(traces)
+        f, B, T = self._first(first, mtr)
+        if against not in AGAINST or rule not in RULES:
+            raise TspwsError(f"against must be one of {tuple(AGAINST)} and rule one of {tuple(RULES)}, got {against!r}, {rule!r}")
+        n0, n1 = self._window(window)
+        ls = torch.empty((B, self.N), dtype=torch.float32, device=traces.device)
+        ts = torch.empty((B, self.N), dtype=torch.float32, device=traces.device)
+        sel = np.zeros(T, np.int8)
+        kept = np.zeros(B, np.uint32)
+        done = C.c_uint()
+        check(self.lib.tspws_hip_selective_stack_batch(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, AGAINST[against],
+                                                       RULES[rule], float(a), int(iters), n0, n1, ls.data_ptr(), ts.data_ptr(), sel.ctypes.data,
+                                                       kept.ctypes.data, C.byref(done), self._stream()), "selective_stack_batch")
+        return ls, ts, sel, kept, done.value
+
     def _refs(self, t, name, rows):
         """Data pointer of a reference array: contiguous float32 [rows][N] (or [N] for one row) on the plan's device."""
         import torch
@@ -818,6 +908,9 @@ class Plan:
 
 
 SCHEDULES = ("single", "split", "sharded-finish")
+# tspws_selection_from_scores' rules and the selective stack's reference row, by name
+RULES = {"threshold": 0, "mad": 1}
+AGAINST = {"ls": 0, "ts": 1}
 
 
 def stack_sharded(plan, traces, first=0, mtr_global=None, group=None, schedule=None):
@@ -1085,6 +1178,31 @@ def bootstrap_counts_batch(first, M):
     if load().tspws_bootstrap_plan_batch(cnt.ctypes.data, f.ctypes.data, f.size - 1, int(M)):
         raise TspwsError("tspws_bootstrap_plan_batch refused its arguments")
     return cnt
+
+
+def selection_from_scores(score, first, rule, a):
+    """One mask row from one plane of scores (tspws_selection_from_scores): `score` = float64 [T] (usually the sim plane of one reference,
+    T = first[-1] - first[0]), `rule` = "threshold" / 0 (keep iff score >= a) or "mad" / 1 (per ensemble over its finite scores: keep iff
+    score >= median - a * 1.4826 * MAD).  NaN is never kept.  Returns (sel int8 [T], kept uint32 [B])."""
+    import numpy as np
+    f = np.asarray(first)
+    if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu" or (f < 0).any() or (np.diff(f) < 0).any():
+        raise TspwsError("first must be a 1-D array of B + 1 non-decreasing, non-negative integer offsets")
+    f = np.ascontiguousarray(f, dtype=np.uint64)
+    if hasattr(score, "detach"):
+        score = score.detach().cpu().numpy()
+    sc = np.ascontiguousarray(score, dtype=np.float64)
+    if sc.shape != (int(f[-1] - f[0]),):
+        raise TspwsError(f"score must be one plane of {int(f[-1] - f[0])} scores, got {sc.shape}")
+    r = RULES.get(rule, rule)
+    if r not in (0, 1):
+        raise TspwsError(f"rule must be one of {tuple(RULES)} (or 0 / 1), got {rule!r}")
+    sel = np.zeros(sc.size, np.int8)
+    kept = np.zeros(f.size - 1, np.uint32)
+    rc = load().tspws_selection_from_scores(sel.ctypes.data, kept.ctypes.data, sc.ctypes.data, f.ctypes.data, f.size - 1, int(r), float(a))
+    if rc:
+        raise TspwsError(f"tspws_selection_from_scores refused its arguments (code {rc})")
+    return sel, kept
 
 
 def selection_classes(sel):

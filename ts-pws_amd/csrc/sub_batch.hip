@@ -260,6 +260,46 @@ extern "C" int tspws_subsampling_plan_batch(char *sel, const size_t *first, unsi
 	return 0;
 }
 
+// median of v[0 .. n) (n > 0; sorted in place): for an even count 0.5 * (lo + hi) of the two middle order statistics
+static double median_inplace(double *v, size_t n)
+{
+	std::sort(v, v + n);
+	return n & 1 ? v[n / 2] : 0.5 * (v[n / 2 - 1] + v[n / 2]);
+}
+
+extern "C" int tspws_selection_from_scores(char *sel, unsigned *kept, const double *score, const size_t *first, unsigned B, int rule, double a)
+{
+#pragma clang fp contract(off) // med - a * 1.4826 * mad, every operation rounded on its own
+	if (!sel || !score || !first) return 1;
+	for (unsigned b = 0; b < B; b++) if (first[b + 1] < first[b]) return 1;
+	if ((rule != 0 && rule != 1) || a != a) return 2;
+	std::vector<double> v;
+	for (unsigned b = 0; b < B; b++) {
+		const size_t c0 = first[b] - first[0], m = first[b + 1] - first[b];
+		double thr = a;
+		bool any = true;
+		if (rule == 1) { // robust: median and scaled median absolute deviation of the ensemble's finite scores
+			v.clear();
+			for (size_t i = 0; i < m; i++) if (std::isfinite(score[c0 + i])) v.push_back(score[c0 + i]);
+			any = !v.empty();
+			if (any) {
+				const double med = median_inplace(v.data(), v.size());
+				for (double &x : v) x = fabs(x - med);
+				const double mad = median_inplace(v.data(), v.size());
+				thr = med - a * 1.4826 * mad;
+			}
+		}
+		unsigned k = 0;
+		for (size_t i = 0; i < m; i++) { // (NaN fails every >=)
+			const char keep = any && score[c0 + i] >= thr ? 1 : 0;
+			sel[c0 + i] = keep;
+			k += keep;
+		}
+		if (kept) kept[b] = k;
+	}
+	return 0;
+}
+
 extern "C" int tspws_hip_subsample_batch_sel(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *h_first, unsigned B, unsigned M,
                                              const char *h_sel, float *d_ls_out, float *d_ts_out, unsigned *h_mtr_out, void *s)
 {
