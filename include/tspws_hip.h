@@ -454,6 +454,63 @@ typedef struct {
 } tspws_hip_boot_batch_stats;
 int  tspws_hip_bootstrap_batch_stats(const tspws_hip_plan *plan, tspws_hip_boot_batch_stats *stats);
 
+/* ---- real-weighted stacks ------------------------------------------------------------------------- */
+/* M real-weighted stacks of each of B single-stage ensembles of one trace array in ONE call: the soft counterpart of a mask row or a count
+ * row (days weighted by 1 / energy, by similarity^p, by an SNR; several weightings side by side).  Ensembles, offsets, ld and the layout of
+ * h_w ([M][T] doubles, T = h_first[B] - h_first[0], column i - h_first[0] for trace i) are those of tspws_hip_bootstrap_batch_cnt.  The
+ * reference's linear stack has a hook for this (tspws_stacks_float's w, ts_pws1f_lib.c:485-490) that nothing passes and that leaves the
+ * phase stack and the normalisers unweighted; scaling a copy of the traces cannot say it either, since w Y / |w Y| = Y / |Y|.  For row m of
+ * ensemble b, with w_i = h_w[m][i - h_first[0]] >= 0:
+ *   a trace with w_i == 0 takes no part at all: its coefficients, phasors and samples never reach a sum, exactly like a masked-out trace;
+ *   n+ = the traces with w_i > 0 = h_mtr_out[b][m] (tspws_hip_replica_bands runs on the rows as on the other calls' rows);
+ *   W = sum w_i and Q = sum w_i^2, in FP64, on the host, in trace order; Keff = W W / Q, the effective number of traces, to h_keff[b][m]
+ *     (h_keff: NULL or [B][M] host doubles; 0 when n+ == 0).  For 0/1 rows W = Keff = K exactly;
+ *   ST = sum w_i Y_i, PS = sum w_i Y_i / |Y_i| (the phasor rule of the stacks), in trace order, each trace summed over its splits first, one
+ *     fused multiply-add per component (w in {0, 1}: the bits of an addition);
+ *   the coherence is c = |PS| / W.  For random phases E |PS|^2 = Q, so the bias of c^2 is Q / W^2 = 1 / Keff, and with OUT = the weighted
+ *     coefficient:  unbiased (wu == 2 && unbiased && n+ != 1): OUT = ST (Keff c^2 - 1) / (Keff - 1) / W;  biased, wu == 2: ST |PS|^2 / (W^2 W);
+ *     wu == 1: ST |PS| / (W W);  any other wu: ST (|PS| / W)^wu / W.  n+ == 1 takes the K = 1 rule (:972), and so does a row whose Keff is exactly 1 in FP64 (one weight carries
+ *     the row: Keff - 1 == 0).  A Keff just above 1 keeps the formula, which then amplifies the rounding of c^2 by 1 / (Keff - 1): a row that
+ *     one trace dominates has no bias to average away -- read h_keff.  The expressions are those of the
+ *     other batched calls with (W, Keff) in place of (K, K): a 0/1 row gives the bits of tspws_hip_subsample_batch_sel on that row as a mask;
+ *   tsPWS_out[b][m] = (float) Re_rec(OUT);
+ *   ls_out[b][m] = the FLOAT accumulator of the resampling body (:538-542) with a weighted addend, acc = (float)((double)acc + w_i *
+ *     (double)x_i[n]) (the product rounded on its own) over the participating traces in trace order, times (float)(1. / W) (:579-583).
+ * Multiplying a row by a power of two leaves its outputs bit for bit (short of overflow and underflow).  n+ == 0 gives zero rows, count 0
+ * and Keff 0; an empty ensemble gives the same.  d_ls_out / d_ts_out are [B][M][max] floats on the device, h_mtr_out [B][M] on the host.
+ * B == 0 or M == 0 returns 0 and does nothing.  NULL plan / p / h_first / h_w / outputs / h_mtr_out, NULL traces with T > 0, decreasing
+ * offsets, ld < max, more than 2^32 - 16 traces in an ensemble, a weight inside an ensemble that is NaN, infinite or negative (the message
+ * says "weight"), a row of an ensemble whose W or Q is not finite or whose Q underflows to zero, and a non-empty two-stage ensemble
+ * (0 < Kmax <= M_b; the message says "two-stage": with real weights the groups floor(k Kmax / K) have no meaning -- by design, not a gap)
+ * return TSPWS_E_ARG ("weighted_stack_batch: ...") before any device work, outputs untouched; the checks that need no plan come first.
+ * Fold and mean removal stay with the caller.
+ * In rounds of whole ensembles: the traces are transformed once (one forward launch sequence per stretch of contiguous traces), ONE
+ * segmented weighted accumulation (coefficient tile x group of 8 rows x ensemble; the 8 weights of a trace in one aligned 64-byte block,
+ * read through a wave-uniform address; a zero weight is a wave-uniform skip) leaves every row's ST / PS planes, written once, ONE kernel
+ * forms the float-accumulator linear stacks, then the weights with each row's (n+, W, Keff), the batched inverses and the float epilogue
+ * scattered to [b][m].  Nothing is atomic, every sum has a fixed order: a repeated call is bit-identical.  Every scratch block that grows
+ * with the batch stays within TSPWS_PART_MB (a round never splits an ensemble; one ensemble alone may exceed it).  The call uploads its
+ * tables and waits for `stream`: on return the outputs are complete. */
+int  tspws_hip_weighted_stack_batch(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, const size_t *h_first, unsigned B,
+                                    unsigned M, const double *h_w, float *d_ls_out, float *d_ts_out, unsigned *h_mtr_out, double *h_keff,
+                                    void *stream);
+/* How the plan's last tspws_hip_weighted_stack_batch call with B > 0 and M > 0 went (all zero before the first one). */
+typedef struct {
+	unsigned shared;    /* ensembles that went through the segmented weighted accumulation  */
+	unsigned empty;     /* ensembles without traces (zero rows, zero counts)                */
+	unsigned rounds;    /* rounds forced by the scratch budget (a round never splits an ensemble) */
+	unsigned rows;      /* weight rows finished: M per non-empty ensemble                   */
+} tspws_hip_weighted_batch_stats;
+int  tspws_hip_weighted_stack_batch_stats(const tspws_hip_plan *plan, tspws_hip_weighted_batch_stats *stats);
+/* Host: one weight row from one plane of tspws_hip_trace_scores.  score is [T] doubles, T = first[B] - first[0]; w receives [T] doubles
+ * (one row of h_w).
+ *   rule 0 (a similarity plane): w = score > 0 ? pow(score, a) : 0 -- NaN and non-positive scores give 0.
+ *   rule 1 (the energy plane): w = 1 / score for a finite score > 0, else 0; then divided by the largest w of the ensemble, so that a
+ *           row's W cannot overflow; an ensemble without a positive finite score gets zeros.  a is ignored.
+ * Returns 0; 1 for NULL w / score / first or decreasing offsets (nothing written); 2 for an unknown rule, or a NaN a under rule 0 (nothing
+ * written). */
+int  tspws_weights_from_scores(double *w, const double *score, const size_t *first, unsigned B, int rule, double a);
+
 /* ---- percentile bands of replicas ---------------------------------------------------------------- */
 /* Per sample, Q quantiles over the replicas of each of B ensembles.  d_rows is [B][M][ld] floats on the plan's device (what the batched
  * resampling calls write as d_ls_out / d_ts_out: ld = max), h_mtr NULL or [B][M] host counts (their h_mtr_out): replica (b, m) takes part

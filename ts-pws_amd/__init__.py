@@ -149,6 +149,9 @@ SYMBOLS = {
     "tspws_hip_bootstrap_batch_cnt": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_bootstrap_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _u, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_bootstrap_batch_stats": (_i, [_vp, _vp]),
+    "tspws_hip_weighted_stack_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tspws_hip_weighted_stack_batch_stats": (_i, [_vp, _vp]),
+    "tspws_weights_from_scores": (_i, [_vp, _vp, _vp, _u, _i, _d]),
     "tspws_hip_replica_bands": (_i, [_vp, _vp, _sz, _u, _u, _vp, _vp, _u, _vp, _vp]),
     "tspws_hip_replica_bands_stats": (_i, [_vp, _vp]),
     "tspws_hip_trace_scores": (_i, [_vp, _vp, _sz, _vp, _u, _vp, _sz, _u, _sz, _sz, _vp, _vp, _vp]),
@@ -705,6 +708,53 @@ class Plan:
         check(self.lib.tspws_hip_bootstrap_batch_stats(self.h, C.byref(st)), "bootstrap_batch_stats")
         return dict(zip(("shared", "empty", "rounds", "rows", "max_count"), list(st)))
 
+    def weighted_stack_batch(self, traces, first, w, ls_out=None, ts_out=None, mtr_out=None):
+        """M real-weighted stacks of each of B single-stage ensembles of one trace array in ONE call (tspws_hip_weighted_stack_batch): ensemble
+        b = rows [first[b], first[b+1]) of the float32 [mtr][N] device tensor `traces`; `w` = [M][T] float64 weights >= 0, T = first[B] -
+        first[0], w[m][i - first[0]] = the weight of trace i in row m (weights_from_scores makes such rows).  Returns ls_out[B][M][N],
+        ts_out[B][M][N] (float32 cuda), mtr_out[B][M] (uint32, the traces with a positive weight) and keff[B][M] (float64, the effective number
+        of traces (sum w)^2 / sum w^2): ST = sum w Y, PS = sum w Y / |Y|, coherence |PS| / sum w, the unbiased weight with Keff.  A trace with
+        weight 0 takes no part; a row without weight and an empty ensemble give zero rows, count 0 and keff 0; a 0/1 row is subsample_batch's
+        row on that mask, bit for bit.  NaN, infinite and negative weights and two-stage ensembles (0 < Kmax <= traces) are refused.
+        Synchronises."""
+        import numpy as np
+        import torch
+        mtr, ld = self._traces(traces)
+        f = np.asarray(first)
+        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
+            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
+        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
+            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
+        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
+        B, T = f.size - 1, int(f[-1] - f[0])
+        if not isinstance(w, np.ndarray) or w.ndim != 2 or w.dtype != np.float64:
+            raise TspwsError("weights must be a 2-D float64 numpy array [M][T]")
+        if w.shape[1] != T:
+            raise TspwsError(f"weights must be [M][{T}] (row x trace of the batch), got {w.shape}")
+        w = np.ascontiguousarray(w)
+        Mn = w.shape[0]
+        dev = traces.device
+        ls_out = torch.empty((B, Mn, self.N), dtype=torch.float32, device=dev) if ls_out is None else ls_out
+        ts_out = torch.empty((B, Mn, self.N), dtype=torch.float32, device=dev) if ts_out is None else ts_out
+        mtr_out = np.zeros((B, Mn), np.uint32) if mtr_out is None else mtr_out
+        if not isinstance(mtr_out, np.ndarray) or mtr_out.dtype != np.uint32 or mtr_out.shape != (B, Mn) or not mtr_out.flags.c_contiguous:
+            raise TspwsError(f"mtr_out must be a contiguous uint32 numpy array [{B}][{Mn}]")
+        for t, name in ((ls_out, "ls_out"), (ts_out, "ts_out")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (B, Mn, self.N) or not t.is_contiguous() or \
+                    not t.is_cuda or (t.device.index or 0) != self.device:
+                raise TspwsError(f"{name} must be a contiguous float32 [{B}][{Mn}][{self.N}] tensor on cuda:{self.device}")
+        keff = np.zeros((B, Mn), np.float64)
+        check(self.lib.tspws_hip_weighted_stack_batch(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, Mn, w.ctypes.data,
+                                                      ls_out.data_ptr(), ts_out.data_ptr(), mtr_out.ctypes.data, keff.ctypes.data, self._stream()),
+              "weighted_stack_batch")
+        return ls_out, ts_out, mtr_out, keff
+
+    def weighted_stack_batch_stats(self):
+        """How the last weighted_stack_batch call with B > 0 and M > 0 went (tspws_hip_weighted_stack_batch_stats): dict of counts."""
+        st = (C.c_uint * 4)()
+        check(self.lib.tspws_hip_weighted_stack_batch_stats(self.h, C.byref(st)), "weighted_stack_batch_stats")
+        return dict(zip(("shared", "empty", "rounds", "rows"), list(st)))
+
     def replica_bands(self, rows, q, mtr=None, out=None):
         """Per sample, the quantiles `q` (a sequence of at most 8 probabilities in [0, 1]) over the replicas of each of B ensembles
         (tspws_hip_replica_bands): `rows` = float32 cuda [B][M][N] replica rows (ls_out / ts_out of the batched resampling calls), contiguous
@@ -1203,6 +1253,35 @@ def selection_from_scores(score, first, rule, a):
     if rc:
         raise TspwsError(f"tspws_selection_from_scores refused its arguments (code {rc})")
     return sel, kept
+
+
+# tspws_weights_from_scores' rules, by name
+WEIGHT_RULES = {"power": 0, "inverse": 1}
+
+
+def weights_from_scores(score, first, rule, a=1.0):
+    """One weight row from one plane of scores (tspws_weights_from_scores): `score` = float64 [T] (T = first[-1] - first[0]), `rule` =
+    "power" / 0 (a similarity plane: w = score ** a where score > 0, else 0) or "inverse" / 1 (the energy plane: w = 1 / score for a finite
+    score > 0, else 0, divided by the ensemble's largest w; `a` is ignored).  NaN scores give weight 0.  Returns w float64 [T], one row of
+    Plan.weighted_stack_batch's weights."""
+    import numpy as np
+    f = np.asarray(first)
+    if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu" or (f < 0).any() or (np.diff(f) < 0).any():
+        raise TspwsError("first must be a 1-D array of B + 1 non-decreasing, non-negative integer offsets")
+    f = np.ascontiguousarray(f, dtype=np.uint64)
+    if hasattr(score, "detach"):
+        score = score.detach().cpu().numpy()
+    sc = np.ascontiguousarray(score, dtype=np.float64)
+    if sc.shape != (int(f[-1] - f[0]),):
+        raise TspwsError(f"score must be one plane of {int(f[-1] - f[0])} scores, got {sc.shape}")
+    r = WEIGHT_RULES.get(rule, rule)
+    if r not in (0, 1):
+        raise TspwsError(f"rule must be one of {tuple(WEIGHT_RULES)} (or 0 / 1), got {rule!r}")
+    w = np.zeros(sc.size, np.float64)
+    rc = load().tspws_weights_from_scores(w.ctypes.data, sc.ctypes.data, f.ctypes.data, f.size - 1, int(r), float(a))
+    if rc:
+        raise TspwsError(f"tspws_weights_from_scores refused its arguments (code {rc})")
+    return w
 
 
 def selection_classes(sel):

@@ -1,5 +1,5 @@
 // batch_host.h -- host code that the batched entry points share (batch.hip, jk_single.hip, jk_batch.hip, jk_batch_two_stage.hip, conv_batch.hip,
-// sub_batch.hip, boot_batch.hip): the lifetime of a call's uploads, the layout of a table block, the planning of rounds and finish batches, and the small loops
+// sub_batch.hip, boot_batch.hip, weighted_batch.hip): the lifetime of a call's uploads, the layout of a table block, the planning of rounds and finish batches, and the small loops
 // over a selection that every unit needs.  Only what removes knowledge from its call sites lives here; the kernels they share are in batch_kernels.h.
 #pragma once
 

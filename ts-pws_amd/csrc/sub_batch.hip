@@ -377,3 +377,26 @@ extern "C" int tspws_hip_subsample_batch_stats(const tspws_hip_plan *pl, tspws_h
 	*stats = pl->sub_batch_stats;
 	return 0;
 }
+
+extern "C" int tspws_weights_from_scores(double *w, const double *score, const size_t *first, unsigned B, int rule, double a)
+{
+	if (!w || !score || !first) return 1;
+	for (unsigned b = 0; b < B; b++) if (first[b + 1] < first[b]) return 1;
+	if ((rule != 0 && rule != 1) || (rule == 0 && a != a)) return 2;
+	for (unsigned b = 0; b < B; b++) {
+		const size_t c0 = first[b] - first[0], m = first[b + 1] - first[b];
+		if (rule == 0) { // a power of a similarity (NaN fails the >)
+			for (size_t i = 0; i < m; i++) w[c0 + i] = score[c0 + i] > 0 ? pow(score[c0 + i], a) : 0.;
+			continue;
+		}
+		// inverse energy, the ensemble's largest weight = 1
+		double top = 0;
+		for (size_t i = 0; i < m; i++) {
+			const double s = score[c0 + i];
+			w[c0 + i] = s > 0 && std::isfinite(s) ? 1. / s : 0.;
+			top = std::max(top, w[c0 + i]);
+		}
+		if (top > 0) for (size_t i = 0; i < m; i++) w[c0 + i] /= top;
+	}
+	return 0;
+}

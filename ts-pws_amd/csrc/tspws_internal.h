@@ -16,6 +16,7 @@
 //   conv_batch.hip  convergence curves of many ensembles in one call
 //   sub_batch.hip   random subsamples of many ensembles in one call
 //   boot_batch.hip  bootstrap replicas of many ensembles in one call
+//   weighted_batch.hip  real-weighted stacks of many ensembles in one call
 //   replica_bands.hip  percentile bands over the replica rows those calls leave (its own table slot, SCR_RBTAB)
 //   trace_scores.hip   similarity / misfit of every trace against reference rows, the selective stack (its own slots: SCR_TSTAB the group
 //                 table, SCR_TSP the partial sums, SCR_TSOUT the selective stack's score planes)
@@ -289,6 +290,7 @@ struct tspws_hip_plan {
 	tspws_hip_conv_batch_stats conv_batch_stats{}; // ... and the last batched convergence curves (conv_batch.hip)
 	tspws_hip_sub_batch_stats sub_batch_stats{}; // ... and the last batched random subsampling (sub_batch.hip)
 	tspws_hip_boot_batch_stats boot_batch_stats{}; // ... and the last batched bootstrap (boot_batch.hip)
+	tspws_hip_weighted_batch_stats weighted_batch_stats{}; // ... and the last batched weighted stack (weighted_batch.hip)
 	tspws_hip_bands_stats bands_stats{}; // ... and the last percentile bands (replica_bands.hip)
 	tspws_hip_trace_scores_stats_t trace_scores_stats{}; // ... and the last trace scores (trace_scores.hip)
 };
@@ -360,7 +362,9 @@ __device__ __forceinline__ void add_unit_phasor(double2 &ps, const double2 v)
 	}
 }
 
-__device__ __forceinline__ double2 weight_value(const double2 st, const double2 ps, const int mode, const double K, const double M, const double wu)
+// K normalises the phase stack, Kb is the count whose reciprocal is the bias of the squared coherence (mode 3 only), M normalises the linear
+// stack.  The stacks of the reference have K == Kb; a real-weighted stack (weighted_batch.hip) has K = M = sum w and Kb = (sum w)^2 / sum w^2.
+__device__ __forceinline__ double2 weight_value_eff(const double2 st, const double2 ps, const int mode, const double K, const double Kb, const double M, const double wu)
 {
 	double a;
 	if (mode == 0) {
@@ -376,11 +380,16 @@ __device__ __forceinline__ double2 weight_value(const double2 st, const double2 
 		a = pow(a, wu);
 		return make_double2(st.x * a / M, st.y * a / M);
 	}
-	const double iK = 1. / K, iK1 = 1. / (K - 1), iM = 1. / M;
+	const double iK = 1. / K, iK1 = 1. / (Kb - 1), iM = 1. / M;
 	const double px = ps.x * iK, py = ps.y * iK;
 	a = px * px + py * py;
-	a = (K * a - 1) * iK1;
+	a = (Kb * a - 1) * iK1;
 	return make_double2(st.x * a * iM, st.y * a * iM);
+}
+
+__device__ __forceinline__ double2 weight_value(const double2 st, const double2 ps, const int mode, const double K, const double M, const double wu)
+{
+	return weight_value_eff(st, ps, mode, K, K, M, wu);
 }
 #endif
 
