@@ -135,6 +135,33 @@ typedef struct {
 } tspws_hip_inverse_info_t;
 int  tspws_hip_inverse_info(const tspws_hip_plan *plan, tspws_hip_inverse_info_t *info);
 
+/* ---- band rows: the reconstruction per range of scales, with its quadrature ------------ */
+/* The reconstruction is a sum over the S scales (x^ = sum_s x_s, x_s = gain_s D_s sum Re(conj(wd_s[l]) Y_s[..]): csrc/inv_poly.h).  A band
+ * is a half-open scale range [s_begin, s_end), 0 <= s_begin <= s_end <= S; bands of one table may overlap, cut a decimation octave between
+ * two voices, or be empty.  For a coefficient set Y and a band r, in FP64,
+ *   X_r = sum_{s in band} x_s,   Q_r = sum_{s in band} q_s   (added in increasing s),   E_r[n] = hypot(X_r[n], Q_r[n])
+ * where q_s is x_s with Im in place of Re: the real row of the set -i Y = (Im Y, -Re Y), i.e. the band-limited signal's quadrature, and E_r
+ * its envelope.  The row of a band does not depend on which other bands the table holds, bit for bit: every scale inside at least one
+ * band is one work item of the polyphase kernel, whatever the table, and a combining kernel adds a band's scale rows in increasing s. */
+typedef struct { unsigned s_begin, s_end; } tspws_band;
+#define TSPWS_MAX_BANDS 1024u
+/* X_r (d_re) and Q_r (d_im; NULL: real rows only, no quadrature work) of nset coefficient sets d_Y[nset][ncoef], as [nset][R][N] doubles.
+ * Each set is read once.  An empty band gives zero rows; R = 0 or nset = 0 returns 0 and does nothing.  A NULL plan / d_Y / h_bands / d_re,
+ * s_end > S, s_begin > s_end and R > TSPWS_MAX_BANDS return TSPWS_E_ARG ("inverse_bands: ...") before any device work, outputs untouched;
+ * the checks that need no plan come first.
+ * The scale rows of a batch of sets (scales inside a band x N doubles per set, twice that with the quadrature) stay within TSPWS_PART_MB.
+ * The work is ordered on `stream`; a call whose band table differs from the plan's previous one first waits for `stream` (the device copy
+ * of the table is the plan's).  Sweeps builds: TSPWS_INV_GENERIC does not apply (band rows always take the polyphase kernel). */
+int  tspws_hip_inverse_bands(tspws_hip_plan *plan, const double *d_Y, size_t nset, const tspws_band *h_bands, unsigned R,
+                             double *d_re, double *d_im, void *stream);
+/* Host rule, no device: bands of centre frequencies.  fc_s = w0 / (2 PI dt scale_s) (the reference's relation between fmin and the largest
+ * scale, ts_pws1f_lib.c:112, operations in that order; decreasing in s, written to fc[S] unless NULL); band r = the scales with
+ * f_lo[r] <= fc_s < f_hi[r] -- a contiguous range, and bands with shared edges partition the scales between the outer edges.  A band above
+ * or below every fc_s is empty.  A NULL scale / f_lo / f_hi / bands (with R > 0), a non-finite edge, f_lo > f_hi and dt <= 0 (or not
+ * finite) return TSPWS_E_ARG. */
+int  tspws_bands_from_frequencies(const double *scale, unsigned S, double w0, double dt, const double *f_lo, const double *f_hi, unsigned R,
+                                  tspws_band *bands, double *fc);
+
 /* ---- stacks in the time-scale domain ----------------------------------------------- */
 /* ST += sum_b Y_b ; PS += sum_b Y_b/|Y_b| (non-unit quotients skipped); zero_first clears
  * ST/PS before.  The loop body of ts_pws1f_lib.c:486-494 / :897-904. */
@@ -204,6 +231,28 @@ typedef struct {
 	unsigned pass_batches;   /* batches of the many-trace pass (an ensemble may straddle two)                             */
 } tspws_hip_batch_stats;
 int  tspws_hip_stack_batch_stats(const tspws_hip_plan *plan, tspws_hip_batch_stats *stats);
+/* tspws_hip_stack_batch with a band-limited finish: the ensembles, stage rule, weights and rounds are tspws_hip_stack_batch's (single- and
+ * two-stage ensembles may be mixed); with (OUT_b, ST_b) the weighted set and the linear stack that call inverts and M_b the trace count,
+ * the outputs are [B][R][max] floats (tspws_hip_inverse_bands' definitions)
+ *   ts[b][r] = (float) X_r(OUT_b)        ts_env[b][r] = (float) E_r(OUT_b)
+ *   ls[b][r] = (float) X_r(ST_b) / (float) M_b   ls_env[b][r] = (float) E_r(ST_b) / (float) M_b   (the reference's float division, :233-241)
+ * written by the combining kernel itself (no FP64 row in memory).  Each set is read once, whatever R.  d_ls_env and d_ts_env are both NULL
+ * (no quadrature work at all; ls / ts have the same bits either way) or both given.  Empty ensembles and empty bands give zero rows; the
+ * band [0, S) gives tspws_hip_stack_batch's rows to the parity tolerance (relerr 2e-6).  Ensembles that tspws_hip_stack_batch hands to
+ * one tspws_hip_stack each get their sets from tspws_hip_stacks_float, or tspws_hip_partial_stacks + tspws_hip_stacks_double, and
+ * tspws_hip_weight.  Refusals (TSPWS_E_ARG, "stack_batch_bands: ..." before any device work, outputs untouched): tspws_hip_stack_batch's,
+ * tspws_hip_inverse_bands', and exactly one envelope pointer; B = 0 or R = 0 returns 0 and does nothing.  The call waits for `stream`. */
+int  tspws_hip_stack_batch_bands(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, const size_t *h_first, unsigned B,
+                                 const tspws_band *h_bands, unsigned R, float *d_ls, float *d_tsPWS, float *d_ls_env, float *d_tsPWS_env,
+                                 void *stream);
+/* The plan's last tspws_hip_stack_batch_bands call with B > 0 and R > 0 (all zero before the first one). */
+typedef struct {
+	tspws_hip_batch_stats batch; /* tspws_hip_stack_batch's counters                                                         */
+	unsigned finish_batches;     /* batches of sets of the band finish (scale rows within TSPWS_PART_MB)                      */
+	unsigned scales;             /* scales inside at least one band: work items of the inverse, slot rows per set             */
+	unsigned quadrature;         /* 1: the quadrature ran (envelopes asked for)                                               */
+} tspws_hip_stack_bands_stats;
+int  tspws_hip_stack_batch_bands_stats(const tspws_hip_plan *plan, tspws_hip_stack_bands_stats *stats);
 /* Optional timing inside tspws_hip_stack: HIP events on `stream` at the start of the call, after its streaming stage (the
  * partial-stack launches) and at its end, for up to max_calls calls.  _read synchronises the device and returns the per-call
  * durations in ms (either array may be NULL; *ncalls = calls recorded); _end returns the mean of the streaming stage and

@@ -103,6 +103,8 @@ SYMBOLS = {
     "tspws_hip_forward_spectral_f32": (_i, [_vp, _vp, _sz, _sz, _vp, _u, _vp]),
     "tspws_hip_inverse": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "tspws_hip_inverse_info": (_i, [_vp, _vp]),
+    "tspws_hip_inverse_bands": (_i, [_vp, _vp, _sz, _vp, _u, _vp, _vp, _vp]),
+    "tspws_bands_from_frequencies": (_i, [_vp, _u, _d, _d, _vp, _vp, _u, _vp, _vp]),
     "tspws_hip_accumulate": (_i, [_vp, _vp, _sz, _vp, _vp, _i, _vp]),
     "tspws_hip_stacks_double": (_i, [_vp, _vp, _u, _sz, _vp, _vp, _vp]),
     "tspws_hip_stacks_float": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
@@ -116,6 +118,8 @@ SYMBOLS = {
     "tspws_hip_stack": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "tspws_hip_stack_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _vp, _vp, _vp]),
     "tspws_hip_stack_batch_stats": (_i, [_vp, _vp]),
+    "tspws_hip_stack_batch_bands": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _vp, _u, _vp, _vp, _vp, _vp, _vp]),
+    "tspws_hip_stack_batch_bands_stats": (_i, [_vp, _vp]),
     "tspws_hip_profile_begin": (_i, [_vp, _sz]),
     "tspws_hip_profile_read": (_i, [_vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "tspws_hip_profile_end": (_i, [_vp, C.POINTER(_d), C.POINTER(_sz)]),
@@ -341,6 +345,36 @@ class Plan:
         torch.cuda.synchronize(Yd.device)
         return x.cpu().numpy() if isinstance(Y, np.ndarray) else x
 
+    def inverse_bands(self, Y, bands, quadrature=False):
+        """Band rows of the coefficient sets Y[nset][ncoef] in ONE tspws_hip_inverse_bands call: `bands` = R half-open scale ranges
+        (s_begin, s_end), which may overlap, cut an octave between voices or be empty.  Returns X[nset][R][N] (float64) -- row r = the sum of
+        the reconstruction's scale rows s_begin <= s < s_end -- or, with quadrature=True, (X, Q): Q = the same rows of the set -i Y.  Y as for
+        inverse (numpy in, numpy out; device tensor in, device tensors out).  The outputs hold NaN before the call; synchronises."""
+        import numpy as np
+        import torch
+        bt = band_table(bands)
+        if isinstance(Y, np.ndarray):
+            if Y.dtype != np.complex128 or Y.ndim != 2 or Y.shape[1] != self.ncoef or not Y.shape[0]:
+                raise TspwsError(f"Y must be complex128 [nset >= 1][{self.ncoef}], got {Y.dtype} {Y.shape}")
+            Yd = torch.as_tensor(np.ascontiguousarray(Y), device=f"cuda:{self.device}")
+        elif isinstance(Y, torch.Tensor):
+            if Y.dtype != torch.complex128 or Y.dim() != 2 or Y.shape[1] != self.ncoef or not Y.shape[0]:
+                raise TspwsError(f"Y must be complex128 [nset >= 1][{self.ncoef}], got {Y.dtype} {tuple(Y.shape)}")
+            if not Y.is_cuda or (Y.device.index or 0) != self.device or not Y.is_contiguous():
+                raise TspwsError(f"Y must be a contiguous tensor on cuda:{self.device}, got {Y.device}")
+            Yd = Y
+        else:
+            raise TspwsError("Y must be a complex128 numpy array or device tensor")
+        R = bt.shape[0]
+        X = torch.full((Yd.shape[0], R, self.N), float("nan"), dtype=torch.float64, device=Yd.device)
+        Q = torch.full_like(X, float("nan")) if quadrature else None
+        check(self.lib.tspws_hip_inverse_bands(self.h, Yd.data_ptr(), Yd.shape[0], bt.ctypes.data, R, X.data_ptr(), Q.data_ptr() if quadrature else None,
+                                               self._stream()), "inverse_bands")
+        torch.cuda.synchronize(Yd.device)
+        if isinstance(Y, np.ndarray):
+            X, Q = X.cpu().numpy(), (Q.cpu().numpy() if quadrature else None)
+        return (X, Q) if quadrature else X
+
     def stack_local(self, traces, first=0, mtr_global=None):
         mtr, ld = self._traces(traces)
         mtr_global = mtr if mtr_global is None else mtr_global
@@ -524,6 +558,35 @@ class Plan:
         check(self.lib.tspws_hip_stack_batch(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, ls.data_ptr(), ts.data_ptr(),
                                              self._stream()), "stack_batch")
         return ls, ts
+
+    def stack_batch_bands(self, traces, first, bands, envelope=False):
+        """stack_batch with a band-limited finish (tspws_hip_stack_batch_bands): `bands` = R half-open scale ranges (bands_from_frequencies
+        makes them from frequency edges).  Returns ls[B][R][N], ts[B][R][N] (float32 cuda) -- row (b, r) = band r's share of ensemble b's
+        linear stack and ts-PWS -- and, with envelope=True, also ls_env, ts_env: the envelopes hypot(row, its quadrature).  B = 1 is the
+        single-ensemble call.  Empty ensembles and empty bands give zero rows."""
+        import numpy as np
+        import torch
+        mtr, ld = self._traces(traces)
+        f = np.asarray(first)
+        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
+            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
+        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
+            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
+        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
+        bt = band_table(bands)
+        B, R = f.size - 1, bt.shape[0]
+        outs = [torch.full((B, R, self.N), float("nan"), dtype=torch.float32, device=traces.device) for _ in range(4 if envelope else 2)]
+        ptr = [t.data_ptr() for t in outs] + [None] * (4 - len(outs))
+        check(self.lib.tspws_hip_stack_batch_bands(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, bt.ctypes.data, R, *ptr,
+                                                   self._stream()), "stack_batch_bands")
+        return tuple(outs)
+
+    def stack_batch_bands_stats(self):
+        """The last stack_batch_bands call with B > 0 and R > 0 (tspws_hip_stack_batch_bands_stats): batch_stats' counts, the batches of
+        sets of its band finish, the scales with work items and whether the quadrature ran."""
+        st = (C.c_uint * 9)()
+        check(self.lib.tspws_hip_stack_batch_bands_stats(self.h, C.byref(st)), "stack_batch_bands_stats")
+        return dict(zip(("single_pass", "two_stage_pass", "looped", "empty", "rounds", "pass_batches", "finish_batches", "scales", "quadrature"), list(st)))
 
     def batch_stats(self):
         """How the last stack_batch call with B > 0 stacked its ensembles (tspws_hip_stack_batch_stats): dict of counts."""
@@ -1253,6 +1316,48 @@ def selection_from_scores(score, first, rule, a):
     if rc:
         raise TspwsError(f"tspws_selection_from_scores refused its arguments (code {rc})")
     return sel, kept
+
+
+def band_table(bands):
+    """The C band table (uint32 [R][2]: s_begin, s_end) of a sequence of (s_begin, s_end) pairs."""
+    import numpy as np
+    b = np.asarray(bands)
+    if b.size == 0:
+        return np.zeros((0, 2), np.uint32)
+    if b.ndim != 2 or b.shape[1] != 2 or b.dtype.kind not in "iu" or (b < 0).any() or (b > 0xFFFFFFFF).any():
+        raise TspwsError("bands must be a sequence of (s_begin, s_end) pairs of non-negative integers")
+    return np.ascontiguousarray(b, dtype=np.uint32)
+
+
+def bands_from_frequencies(plan_or_tables, dt, edges, w0=None):
+    """Bands of centre frequencies (tspws_bands_from_frequencies, host only): fc_s = w0 / (2 pi dt scale_s), band r = the scales with
+    f_lo <= fc_s < f_hi.  `plan_or_tables` = a Plan, or (scale[S], w0) / a dict with "scale" and "w0" (w0 may also be given by keyword);
+    `edges` = a 1-D sequence of R + 1 increasing frequencies (R bands with shared edges, lowest band first: they partition the scales
+    between the outer edges) or a sequence of R (f_lo, f_hi) pairs.  Returns (bands uint32 [R][2], fc[S])."""
+    import numpy as np
+    if isinstance(plan_or_tables, Plan):
+        scale, w = plan_or_tables.tables()["scale"], plan_or_tables.info.w0
+    elif isinstance(plan_or_tables, dict):
+        scale, w = plan_or_tables["scale"], plan_or_tables.get("w0")
+    else:
+        scale, w = plan_or_tables
+    w = w0 if w0 is not None else w
+    if w is None:
+        raise TspwsError("bands_from_frequencies needs w0")
+    scale = np.ascontiguousarray(scale, dtype=np.float64)
+    e = np.asarray(edges, dtype=np.float64)
+    if e.ndim == 1 and e.size >= 1:
+        lo, hi = e[:-1], e[1:]
+    elif e.ndim == 2 and e.shape[1] == 2:
+        lo, hi = e[:, 0], e[:, 1]
+    else:
+        raise TspwsError("edges must be R + 1 frequencies or R (f_lo, f_hi) pairs")
+    lo, hi = np.ascontiguousarray(lo), np.ascontiguousarray(hi)
+    bands = np.zeros((lo.size, 2), np.uint32)
+    fc = np.zeros(scale.size, np.float64)
+    check(load().tspws_bands_from_frequencies(scale.ctypes.data, scale.size, float(w), float(dt), lo.ctypes.data, hi.ctypes.data, lo.size,
+                                             bands.ctypes.data, fc.ctypes.data), "bands_from_frequencies")
+    return bands, fc
 
 
 # tspws_weights_from_scores' rules, by name

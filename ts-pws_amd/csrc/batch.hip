@@ -17,6 +17,10 @@
 //   finish        per round of stacks: one batched tspws_hip_inverse of the (OUT, ST) pairs, k_batch_epilogue with each row's M_b.
 // Rounds keep every scratch block whose size grows with the ensembles -- per-stack sets, reconstructions, the inverse's octave buffer, the
 // rows, their partials and the streaming pass's chunk sums -- within the parts budget (TSPWS_PART_MB); a round never splits an ensemble.
+//   band finish   tspws_hip_stack_batch_bands: the same passes and rounds, but every round's (OUT, ST) pairs go through the band rows of
+//                 the inverse (inverse.hip: tspws_inverse_bands_run) -- R float rows per output and, on request, their envelopes, written
+//                 by the combining kernel; no FP64 reconstructions, no epilogue.  Ensembles that go to one single call each get their pair
+//                 from the public pieces (looped_bands).
 // Batches that the many-trace rule would not take as a whole, and a batch with a single ensemble of its kind, fall back to one
 // tspws_hip_stack per ensemble.  tspws_hip_stack_batch_stats tells which way the last call's ensembles went.
 #include "tspws_internal.h"
@@ -50,13 +54,18 @@ struct HostTables {
 // stacks of one round: [nr][OUT | ST] (the inverse's rows) and [nr][PS | unused] (ST and PS of a stack share one stride), reconstructions
 struct RoundBufs { double2 *Y, *PS; double *x; };
 
-int round_bufs(tspws_hip_plan *pl, size_t nr, RoundBufs *b)
+// the band-limited finish of tspws_hip_stack_batch_bands (nullptr: tspws_hip_stack_batch's own): the band table and the envelope outputs
+struct BandFinish { const tspws_band *bands; unsigned R; float *ls_env, *ts_env; };
+
+int round_bufs(tspws_hip_plan *pl, size_t nr, RoundBufs *b, const BandFinish *bf = nullptr)
 {
 	const size_t nc = pl->ncoef;
 	void *v;
 	int rc;
 	if ((rc = scratch(pl, SCR_BY, 4 * nr * nc * sizeof(double2), &v))) return rc;
 	b->Y = (double2 *)v; b->PS = b->Y + 2 * nr * nc;
+	b->x = nullptr;
+	if (bf) return 0; // (the band finish keeps no FP64 reconstructions)
 	if ((rc = scratch(pl, SCR_BX, 2 * nr * (size_t)pl->N * sizeof(double), &v))) return rc;
 	b->x = (double *)v;
 	return 0;
@@ -71,9 +80,17 @@ size_t round_size(const tspws_hip_plan *pl, size_t n, size_t extra)
 }
 
 // inverses + epilogue of stacks [j0, j0 + nr) of a list whose output rows / trace counts are the device tables d_row / d_cnt
-int round_finish(tspws_hip_plan *pl, const RoundBufs &b, unsigned nr, const unsigned *d_row, const unsigned *d_cnt, float *d_ls, float *d_ts, hipStream_t st)
+// bf: the band rows of every pair instead, floats straight from the combining kernel (d_row NULL: the stacks are the output rows row0 .. with cnt0 traces)
+int round_finish(tspws_hip_plan *pl, const RoundBufs &b, unsigned nr, const unsigned *d_row, const unsigned *d_cnt, float *d_ls, float *d_ts, hipStream_t st,
+                 const BandFinish *bf, unsigned row0 = 0, unsigned cnt0 = 1)
 {
 	int rc;
+	if (bf) {
+		BandOut out;
+		out.ts = d_ts; out.ls = d_ls; out.ts_env = bf->ts_env; out.ls_env = bf->ls_env;
+		out.d_row = d_row; out.d_cnt = d_cnt; out.row0 = row0; out.cnt0 = cnt0;
+		return tspws_inverse_bands_run(pl, b.Y, 2 * (size_t)nr, bf->bands, bf->R, out, st, &pl->stack_bands_stats.finish_batches, &pl->stack_bands_stats.scales);
+	}
 	if ((rc = tspws_hip_inverse(pl, (const double *)b.Y, 2 * (size_t)nr, b.x, (void *)st))) return rc;
 	hipLaunchKernelGGL(k_batch_epilogue, dim3((pl->N + 255) / 256, nr), dim3(256), 0, st, (const double *)b.x, (size_t)pl->N, d_row, d_cnt, d_ls, d_ts);
 	return 0;
@@ -81,7 +98,7 @@ int round_finish(tspws_hip_plan *pl, const RoundBufs &b, unsigned nr, const unsi
 
 // Single-stage ensembles `ens` (all with traces) through one many-trace pass.
 int batch_single(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *first, const std::vector<unsigned> &ens,
-                 size_t total, float *d_ls, float *d_ts, BatchCall &call)
+                 size_t total, float *d_ls, float *d_ts, BatchCall &call, const BandFinish *bf)
 {
 	const size_t N = pl->N, nc = pl->ncoef, n = ens.size();
 	hipStream_t st = call.stream();
@@ -113,7 +130,7 @@ int batch_single(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t 
 	float *xg = (float *)v;
 	const size_t R = round_size(pl, n, 0);
 	RoundBufs b;
-	if ((rc = round_bufs(pl, R, &b))) return rc;
+	if ((rc = round_bufs(pl, R, &b, bf))) return rc;
 	for (size_t r0 = 0; r0 < n; r0 += R) {
 		const size_t r1 = std::min(n, r0 + R);
 		pl->batch_stats.rounds++;
@@ -157,14 +174,14 @@ int batch_single(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t 
 				j = k;
 			}
 		}
-		if ((rc = round_finish(pl, b, (unsigned)(r1 - r0), d_row + r0, d_cnt + r0, d_ls, d_ts, st))) return rc;
+		if ((rc = round_finish(pl, b, (unsigned)(r1 - r0), d_row + r0, d_cnt + r0, d_ls, d_ts, st, bf))) return rc;
 	}
 	return 0;
 }
 
 // Two-stage ensembles `ens` (Kmax <= M_b): one streaming pass for all their partial-stack rows, the rows through the few-trace forward.
 int batch_two_stage(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *first, const std::vector<unsigned> &ens,
-                    size_t total, float *d_ls, float *d_ts, BatchCall &call, HostTables &chunk_tabs)
+                    size_t total, float *d_ls, float *d_ts, BatchCall &call, HostTables &chunk_tabs, const BandFinish *bf)
 {
 	const size_t N = pl->N, nc = pl->ncoef, n = ens.size();
 	const unsigned K = p->Kmax;
@@ -212,7 +229,7 @@ int batch_two_stage(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size
 	const size_t R = round_size(pl, n, std::max((size_t)K * pl->npart * sizeof(double2), (size_t)K * N * sizeof(double)));
 	const size_t ck_cap = std::max<size_t>(1, tspws_part_budget_bytes() / (((N + 3) & ~(size_t)3) * sizeof(double)));
 	RoundBufs b;
-	if ((rc = round_bufs(pl, R, &b))) return rc;
+	if ((rc = round_bufs(pl, R, &b, bf))) return rc;
 	if ((rc = scratch(pl, SCR_BP, R * K * N * sizeof(double), &v))) return rc;
 	double *rows = (double *)v;
 	if ((rc = scratch(pl, SCR_PART, R * K * pl->npart * sizeof(double2), &v))) return rc;
@@ -235,26 +252,37 @@ int batch_two_stage(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size
 		wa.OUT = b.Y; wa.out_stride = 2 * nc;
 		wa.mode = tspws_weight_mode(p->wu, p->unbiased, K); wa.K = (double)K; wa.wu = p->wu; wa.Mv = d_Mv + r0;
 		tspws_launch_accumulate(pl, part, K, b.Y + nc, b.PS, 1, nullptr, 0, st, (unsigned)nr, (size_t)K * pl->npart, 2 * nc, nullptr, &wa, ScaleRange());
-		if ((rc = round_finish(pl, b, (unsigned)nr, d_row + r0, d_cnt + r0, d_ls, d_ts, st))) return rc;
+		if ((rc = round_finish(pl, b, (unsigned)nr, d_row + r0, d_cnt + r0, d_ls, d_ts, st, bf))) return rc;
 	}
 	return 0;
 }
 
-} // namespace
-
-extern "C" int tspws_hip_stack_batch(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *h_first, unsigned B,
-                                     float *d_ls, float *d_ts, void *s)
+// One ensemble that the batch hands to a single call, for the band finish (tspws_hip_stack writes its floats from inside the inverse): its pair
+// of sets from the public pieces -- tspws_hip_stacks_float, or tspws_hip_partial_stacks + tspws_hip_stacks_double, then tspws_hip_weight.
+int looped_bands(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, size_t m, unsigned b, float *d_ls, float *d_ts, void *s, const BandFinish *bf)
 {
-	if (!pl || !p || !h_first) return fail(TSPWS_E_ARG, "stack_batch: NULL");
-	if (!B) return 0;
-	if (!d_ls || !d_ts) return fail(TSPWS_E_ARG, "stack_batch: NULL output");
-	for (unsigned b = 0; b < B; b++)
-		if (h_first[b + 1] < h_first[b]) return fail(TSPWS_E_ARG, "stack_batch: decreasing ensemble offsets");
-	const size_t N = pl->N;
-	const bool any = h_first[B] > h_first[0];
-	if (any && !d_x) return fail(TSPWS_E_ARG, "stack_batch: NULL traces");
-	if (any && ld < N) return fail(TSPWS_E_ARG, "stack_batch: row stride below the trace length");
-	HIP_TRY(hipSetDevice(pl->device));
+	const size_t N = pl->N, nc = pl->ncoef;
+	RoundBufs rb;
+	int rc;
+	if ((rc = round_bufs(pl, 1, &rb, bf))) return rc;
+	double *OUT = (double *)rb.Y, *ST = (double *)(rb.Y + nc), *PS = (double *)rb.PS;
+	unsigned K = (unsigned)m;
+	if (is_two_stage(p, m)) {
+		void *v;
+		K = p->Kmax;
+		if ((rc = scratch(pl, SCR_BP, (size_t)K * N * sizeof(double), &v))) return rc;
+		if ((rc = tspws_hip_partial_stacks(pl, d_x, ld, m, 0, m, K, (double *)v, N, s))) return rc;
+		if ((rc = tspws_hip_stacks_double(pl, (const double *)v, K, N, ST, PS, s))) return rc;
+	} else if ((rc = tspws_hip_stacks_float(pl, d_x, m, ld, ST, PS, s))) return rc;
+	if ((rc = tspws_hip_weight(pl, OUT, ST, PS, K, (unsigned)m, p->wu, p->unbiased, s))) return rc;
+	return round_finish(pl, rb, 1, nullptr, nullptr, d_ls, d_ts, S_(s), bf, b, (unsigned)m);
+}
+
+// tspws_hip_stack_batch (bf == nullptr) and tspws_hip_stack_batch_bands: the arguments are checked
+int stack_batch_run(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *h_first, unsigned B, float *d_ls, float *d_ts, void *s,
+                    const BandFinish *bf)
+{
+	const size_t N = pl->N, NR = bf ? (size_t)bf->R * N : N; // floats per ensemble of an output
 	hipStream_t st = S_(s);
 	int rc;
 	std::vector<unsigned> one, two; // ensembles with traces by stage rule
@@ -272,20 +300,78 @@ extern "C" int tspws_hip_stack_batch(tspws_hip_plan *pl, const t_tsPWS *p, const
 	auto looped = [&](const std::vector<unsigned> &list) { // one tspws_hip_stack per ensemble
 		pl->batch_stats.looped += (unsigned)list.size();
 		for (unsigned b : list)
-			if (int e = tspws_hip_stack(pl, p, d_x + h_first[b] * ld, ld, h_first[b + 1] - h_first[b], d_ls + (size_t)b * N, d_ts + (size_t)b * N, s)) return e;
+			if (int e = bf ? looped_bands(pl, p, d_x + h_first[b] * ld, ld, h_first[b + 1] - h_first[b], b, d_ls, d_ts, s, bf)
+			               : tspws_hip_stack(pl, p, d_x + h_first[b] * ld, ld, h_first[b + 1] - h_first[b], d_ls + (size_t)b * N, d_ts + (size_t)b * N, s)) return e;
 		return 0;
 	};
 	if (one.size() > 1 && tspws_many_trace_path(pl, n1)) {
 		pl->batch_stats.single_pass = (unsigned)one.size();
-		if ((rc = batch_single(pl, p, d_x, ld, h_first, one, n1, d_ls, d_ts, call))) return rc;
+		if ((rc = batch_single(pl, p, d_x, ld, h_first, one, n1, d_ls, d_ts, call, bf))) return rc;
 	} else if ((rc = looped(one))) return rc;
 	if (two.size() > 1) {
 		pl->batch_stats.two_stage_pass = (unsigned)two.size();
-		if ((rc = batch_two_stage(pl, p, d_x, ld, h_first, two, n2, d_ls, d_ts, call, chunk_tabs))) return rc;
+		if ((rc = batch_two_stage(pl, p, d_x, ld, h_first, two, n2, d_ls, d_ts, call, chunk_tabs, bf))) return rc;
 	} else if ((rc = looped(two))) return rc;
-	if ((rc = zero_empty_ensembles(h_first, B, st, {{d_ls, N}, {d_ts, N}}))) return rc;
+	if ((rc = zero_empty_ensembles(h_first, B, st, {{d_ls, NR}, {d_ts, NR}, {bf ? bf->ls_env : nullptr, NR}, {bf ? bf->ts_env : nullptr, NR}}))) return rc;
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(call.drain()); // outputs complete
+	return 0;
+}
+
+// what tspws_hip_stack_batch refuses of its traces and offsets (who: the entry point's name in the text)
+int batch_args(const char *who, const tspws_hip_plan *pl, const float *d_x, size_t ld, const size_t *h_first, unsigned B)
+{
+	const std::string w(who);
+	for (unsigned b = 0; b < B; b++)
+		if (h_first[b + 1] < h_first[b]) return fail(TSPWS_E_ARG, (w + ": decreasing ensemble offsets").c_str());
+	const bool any = h_first[B] > h_first[0];
+	if (any && !d_x) return fail(TSPWS_E_ARG, (w + ": NULL traces").c_str());
+	if (any && ld < pl->N) return fail(TSPWS_E_ARG, (w + ": row stride below the trace length").c_str());
+	return 0;
+}
+
+} // namespace
+
+extern "C" int tspws_hip_stack_batch(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *h_first, unsigned B,
+                                     float *d_ls, float *d_ts, void *s)
+{
+	if (!pl || !p || !h_first) return fail(TSPWS_E_ARG, "stack_batch: NULL");
+	if (!B) return 0;
+	if (!d_ls || !d_ts) return fail(TSPWS_E_ARG, "stack_batch: NULL output");
+	if (int rc = batch_args("stack_batch", pl, d_x, ld, h_first, B)) return rc;
+	HIP_TRY(hipSetDevice(pl->device));
+	return stack_batch_run(pl, p, d_x, ld, h_first, B, d_ls, d_ts, s, nullptr);
+}
+
+extern "C" int tspws_hip_stack_batch_bands(tspws_hip_plan *pl, const t_tsPWS *p, const float *d_x, size_t ld, const size_t *h_first, unsigned B,
+                                           const tspws_band *h_bands, unsigned R, float *d_ls, float *d_ts, float *d_ls_env, float *d_ts_env, void *s)
+{
+	// (the checks that need no plan first)
+	if (int rc = tspws_bands_check(pl, h_bands, R, "stack_batch_bands")) return rc;
+	if (!d_ls_env != !d_ts_env) return fail(TSPWS_E_ARG, "stack_batch_bands: the two envelope outputs are both NULL or both given");
+	if (h_first)
+		for (unsigned b = 0; b < B; b++)
+			if (h_first[b + 1] < h_first[b]) return fail(TSPWS_E_ARG, "stack_batch_bands: decreasing ensemble offsets");
+	if (!pl || !p || !h_first) return fail(TSPWS_E_ARG, "stack_batch_bands: NULL");
+	if (!B || !R) return 0;
+	if (!h_bands) return fail(TSPWS_E_ARG, "stack_batch_bands: NULL band table");
+	if (!d_ls || !d_ts) return fail(TSPWS_E_ARG, "stack_batch_bands: NULL output");
+	if (int rc = batch_args("stack_batch_bands", pl, d_x, ld, h_first, B)) return rc;
+	HIP_TRY(hipSetDevice(pl->device));
+	pl->stack_bands_stats = tspws_hip_stack_bands_stats();
+	pl->stack_bands_stats.quadrature = d_ls_env ? 1u : 0u;
+	const BandFinish bf = {h_bands, R, d_ls_env, d_ts_env};
+	const tspws_hip_batch_stats plain = pl->batch_stats; // (tspws_hip_stack_batch_stats keeps answering for the last tspws_hip_stack_batch call)
+	const int rc = stack_batch_run(pl, p, d_x, ld, h_first, B, d_ls, d_ts, s, &bf);
+	pl->stack_bands_stats.batch = pl->batch_stats;
+	pl->batch_stats = plain;
+	return rc;
+}
+
+extern "C" int tspws_hip_stack_batch_bands_stats(const tspws_hip_plan *pl, tspws_hip_stack_bands_stats *stats)
+{
+	if (!pl || !stats) return fail(TSPWS_E_ARG, "stack_batch_bands_stats: NULL");
+	*stats = pl->stack_bands_stats;
 	return 0;
 }
 

@@ -63,11 +63,21 @@ struct OctDesc {
 
 // GEN = the three-frame form for octaves whose D does not divide N (its own instantiation: the masked loads and 64-bit
 // index arithmetic would otherwise cost the common case registers and time; the host launches the two classes separately)
-template <int NREC, bool GEN, bool LDSW = false>
+// QUAD (the band rows, tspws_hip_inverse_bands): the same work item also accumulates the quadrature Im(conj(wd) Y) from the same taps and
+// the same coefficient loads -- "set c + 1 = set c rotated by -i on the fly": q = fma(wd.x, y.y, fma(-wd.y, y.x, q)) is, operation for
+// operation, the real part's chain on the set (Im Y, -Re Y) -- and writes it q_off doubles behind the real rows.  Twice the accumulators:
+// instantiated with NREC = 1 only (the register footprint of the NREC = 2 real form).  The other instantiations compile as before.
+#define INV_QSTEP(TP, YW)                                                                                     \
+	if constexpr (QUAD) {                                                                                     \
+		_Pragma("unroll") for (int c = 0; c < NREC; c++)                                                      \
+			_Pragma("unroll") for (int r = 0; r < R; r++)                                                     \
+				accq[c][r] = fma((TP).x, (YW).y, fma(-(TP).y, (YW).x, accq[c][r]));                             \
+	}
+template <int NREC, bool GEN, bool LDSW = false, bool QUAD = false>
 __global__ void __launch_bounds__(256) k_inv_poly(const double2 *__restrict__ Y, size_t ncoef, unsigned N, const ScaleDesc *__restrict__ sc,
                                                   const OctDesc *__restrict__ oc, unsigned noct, const double2 *__restrict__ wd,
                                                   double *__restrict__ obuf, size_t slot_stride, unsigned total_waves, size_t y_coef,
-                                                  size_t y_obuf, unsigned wave_base)
+                                                  size_t y_obuf, unsigned wave_base, size_t q_off = 0)
 {
 	Y += (size_t)blockIdx.y * y_coef; obuf += (size_t)blockIdx.y * y_obuf; // blockIdx.y = independent reconstruction set
 	constexpr int R = INV_R;
@@ -96,6 +106,11 @@ __global__ void __launch_bounds__(256) k_inv_poly(const double2 *__restrict__ Y,
 	for (int c = 0; c < NREC; c++)
 #pragma unroll
 		for (int r = 0; r < R; r++) acc[c][r] = 0;
+	double accq[QUAD ? NREC : 1][R];
+#pragma unroll
+	for (int c = 0; c < (QUAD ? NREC : 1); c++)
+#pragma unroll
+		for (int r = 0; r < R; r++) accq[c][r] = 0;
 
 	if constexpr (LDSW) {
 		// (this instantiation is launched for the waves of the octaves with D <= INV_LDS_MAXD whose D divides N only)
@@ -160,6 +175,7 @@ __global__ void __launch_bounds__(256) k_inv_poly(const double2 *__restrict__ Y,
 #pragma unroll
 							for (int r = 0; r < R; r++)
 								acc[c][r] = fma(tp[u].x, yw[c][(u + r) % R].x, fma(tp[u].y, yw[c][(u + r) % R].y, acc[c][r]));
+						INV_QSTEP(tp[u], yw[c][(u + r) % R])
 					}
 					l += (unsigned)R * D; // (a partial last block leaves l past its steps: the next voice starts over)
 				}
@@ -214,6 +230,7 @@ __global__ void __launch_bounds__(256) k_inv_poly(const double2 *__restrict__ Y,
 #pragma unroll
 								for (int r = 0; r < R; r++)
 									acc[c][r] = fma(tp.x, yw[c][(u + r) % R].x, fma(tp.y, yw[c][(u + r) % R].y, acc[c][r]));
+							INV_QSTEP(tp, yw[c][(u + r) % R])
 						}
 						l += D;
 					}
@@ -264,6 +281,7 @@ __global__ void __launch_bounds__(256) k_inv_poly(const double2 *__restrict__ Y,
 #pragma unroll
 						for (int r = 0; r < R; r++)
 							acc[c][r] = fma(tp.x, yw[c][(u + r) % R].x, fma(tp.y, yw[c][(u + r) % R].y, acc[c][r]));
+					INV_QSTEP(tp, yw[c][(u + r) % R])
 				}
 				l += D;
 			}
@@ -306,6 +324,7 @@ __global__ void __launch_bounds__(256) k_inv_poly(const double2 *__restrict__ Y,
 #pragma unroll
 						for (int r = 0; r < R; r++)
 							acc[c][r] = fma(tp.x, yw[c][(u + r) % R].x, fma(tp.y, yw[c][(u + r) % R].y, acc[c][r]));
+					INV_QSTEP(tp, yw[c][(u + r) % R])
 				}
 				l += D;
 			}
@@ -321,6 +340,7 @@ __global__ void __launch_bounds__(256) k_inv_poly(const double2 *__restrict__ Y,
 				for (int c = 0; c < NREC; c++)
 #pragma unroll
 					for (int r = 0; r < R; r++) acc[c][r] = fma(tp.x, yw[c][r].x, fma(tp.y, yw[c][r].y, acc[c][r]));
+				INV_QSTEP(tp, yw[c][r])
 			}
 #pragma unroll
 			for (int c = 0; c < NREC; c++)
@@ -339,6 +359,10 @@ __global__ void __launch_bounds__(256) k_inv_poly(const double2 *__restrict__ Y,
 		if (k < Ns && n < N) { // (n < N matters only when D does not divide N: the last row is partial)
 #pragma unroll
 			for (int c = 0; c < NREC; c++) dst[(size_t)c * N + n] = acc[c][r];
+			if constexpr (QUAD) {
+#pragma unroll
+				for (int c = 0; c < NREC; c++) dst[q_off + (size_t)c * N + n] = accq[c][r];
+			}
 		}
 	}
 }
@@ -390,4 +414,76 @@ __global__ void __launch_bounds__(256) k_inv_combine_ranges(const double *__rest
 	for (unsigned s = 0; s < na; s++) a += obuf[(size_t)(a0 + s) * slot_stride + i];
 	for (unsigned s = 0; s < nb; s++) a += obuf[(size_t)(b0 + s) * slot_stride + i];
 	xout[i] = a;
+}
+
+// ------------------------------------------------------------------------------------------
+// band rows (tspws_hip_inverse_bands, tspws_hip_stack_batch_bands): every scale inside at least one band is ONE work item of k_inv_poly with
+// a slot row of its own (slot = rank of the scale among those scales, so a band's rows are consecutive), whatever the table -- a scale's row
+// is formed the same way in every call -- and this kernel adds the rows of a band in increasing s.
+//   X_r = sum_{s in band} x_s,  Q_r = sum q_s (FP64),  E_r = hypot(X_r, Q_r)
+// grid = (samples, bands, sets of the finish batch).  Layouts of the slot rows (what the k_inv_poly launches of the batch leave):
+//   quad   set j at j 2 U N: U real rows, then U quadrature rows
+//   else   pairs: set j at (j >> 1) 2 U N + (j & 1) N, rows 2 N apart; the odd last set (j == paired) at paired U N, rows N apart
+// F32 = false: FP64 rows re / im [set0 + j][band][N] (im may be NULL).  F32 = true: the batched stack's floats with no FP64 row in memory --
+// set set0 + j is OUT (even: ts = (float) X, ts_env = (float) E) or ST (odd: ls = (float) X / (float) M, ls_env likewise: the reference's float
+// division) of stack (set0 + j) >> 1, whose output row and trace count are d_row / d_cnt of it (d_row NULL: row0 + stack, cnt0).
+// ------------------------------------------------------------------------------------------
+struct BandSlots { unsigned slot0, n; }; // a band's slot rows [slot0, slot0 + n)
+struct BandCombine {
+	size_t N;
+	unsigned U, paired, set0, quad;
+	const BandSlots *bt;
+	double *re, *im;
+	float *ts, *ls, *ts_env, *ls_env;
+	const unsigned *row, *cnt;
+	unsigned row0, cnt0;
+};
+
+__device__ __forceinline__ double band_sum(const double *__restrict__ src, size_t stride, unsigned n)
+{
+	if (!n) return 0.0;
+	double a = src[0];
+	unsigned s = 1;
+	for (; s + 4 <= n; s += 4) { // four rows in flight, added in row order (k_inv_combine_out)
+		double v[4];
+#pragma unroll
+		for (int j = 0; j < 4; j++) v[j] = src[(size_t)(s + (unsigned)j) * stride];
+#pragma unroll
+		for (int j = 0; j < 4; j++) a += v[j];
+	}
+	for (; s < n; s++) a += src[(size_t)s * stride];
+	return a;
+}
+
+template <bool F32>
+__global__ void __launch_bounds__(256) k_inv_combine_bands(const double *__restrict__ obuf, const BandCombine a)
+{
+	const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (n >= a.N) return;
+	const unsigned r = blockIdx.y, j = blockIdx.z, R = gridDim.y;
+	const BandSlots b = a.bt[r];
+	size_t base, stride;
+	if (a.quad) { base = (size_t)j * 2 * a.U * a.N; stride = a.N; }
+	else if (j < a.paired) { base = (size_t)(j >> 1) * 2 * a.U * a.N + (size_t)(j & 1) * a.N; stride = 2 * a.N; }
+	else { base = (size_t)a.paired * a.U * a.N; stride = a.N; }
+	const double *src = obuf + base + (size_t)b.slot0 * stride + n;
+	const double x = band_sum(src, stride, b.n);
+	const double q = a.quad ? band_sum(src + (size_t)a.U * a.N, stride, b.n) : 0.0;
+	const unsigned set = a.set0 + j;
+	if constexpr (!F32) {
+		const size_t o = ((size_t)set * R + r) * a.N + n;
+		a.re[o] = x;
+		if (a.im) a.im[o] = q;
+	} else {
+		const unsigned k = set >> 1;
+		const size_t o = ((size_t)(a.row ? a.row[k] : a.row0 + k) * R + r) * a.N + n;
+		if (set & 1) {
+			const float m = (float)(a.cnt ? a.cnt[k] : a.cnt0);
+			a.ls[o] = (float)x / m;
+			if (a.ls_env) a.ls_env[o] = (float)hypot(x, q) / m;
+		} else {
+			a.ts[o] = (float)x;
+			if (a.ts_env) a.ts_env[o] = (float)hypot(x, q);
+		}
+	}
 }

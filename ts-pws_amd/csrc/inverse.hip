@@ -123,6 +123,7 @@ __global__ void __launch_bounds__(256) k_inverse_generic(const double2 *__restri
 }
 
 #include "inv_poly.h"
+#include "batch_host.h"
 
 // octaves up to this decimation take the LDS-staged instantiation (TSPWS_INV_LDS_MAXD, default 1: the full-rate scales of the
 // Mexican hat / `uni` frames, whose per-lane windows touch 64 cache lines per wave-load; 0: none)
@@ -312,6 +313,202 @@ extern "C" int tspws_hip_inverse_info(const tspws_hip_plan *p, tspws_hip_inverse
 	info->per_scale = p->inv_noct == p->S ? 1u : 0u;
 	info->waves = p->inv_waves; info->waves_lds = p->inv_waves_lds; info->waves_fast = p->inv_waves_fast;
 	info->generic = (tspws_generic_inverse() || p->inv_noct == 0) ? 1u : 0u;
+	return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// band rows (include/tspws_hip.h: tspws_hip_inverse_bands; kernels: inv_poly.h)
+// ------------------------------------------------------------------------------------------
+// The per-scale work list -- one item per scale, the geometry of the `split` form of tspws_build_inverse whatever the frame's length -- is built
+// at the first band call and kept here, apart from d_oc: the list tspws_hip_inverse launches is not touched.  A call selects the scales inside at
+// least one band (scale order inside a class, D divides N first: the launch classes of inv_launch_waves), gives them consecutive waves and the
+// slot rows 0 .. U - 1 in scale order, and uploads that list and the bands' slot ranges; the device copies are the plan's, so a call with another
+// table than the last one waits for the stream first, and a call with the same table uploads nothing.
+struct BandTables {
+	std::vector<OctDesc> per_scale;  // item of every scale (wave_off / slot are set per table)
+	std::vector<tspws_band> table;   // the table the device copies were made for
+	bool valid = false;
+	unsigned U = 0, waves = 0, waves_lds = 0, waves_fast = 0;
+	OctDesc *d_oc = nullptr;         // [S]
+	BandSlots *d_bt = nullptr;       // [TSPWS_MAX_BANDS]
+};
+
+void tspws_bands_destroy(tspws_hip_plan *p)
+{
+	if (!p->bands) return;
+	if (p->bands->d_oc) (void)hipFree(p->bands->d_oc);
+	if (p->bands->d_bt) (void)hipFree(p->bands->d_bt);
+	delete p->bands;
+	p->bands = nullptr;
+}
+
+// what a band table is refused for; the checks that need no plan come first (p / bands NULL: what needs them is left out -- the entry points
+// refuse the NULL itself afterwards)
+int tspws_bands_check(const tspws_hip_plan *p, const tspws_band *bands, unsigned R, const char *who)
+{
+	const std::string w(who);
+	if (R > TSPWS_MAX_BANDS) return fail(TSPWS_E_ARG, (w + ": more than 1024 bands").c_str());
+	if (!bands) return 0;
+	for (unsigned r = 0; r < R; r++)
+		if (bands[r].s_begin > bands[r].s_end) return fail(TSPWS_E_ARG, (w + ": a band with s_begin > s_end").c_str());
+	if (!p) return 0;
+	for (unsigned r = 0; r < R; r++)
+		if (bands[r].s_end > p->S) return fail(TSPWS_E_ARG, (w + ": a band ends behind the last scale").c_str());
+	return 0;
+}
+
+static int bands_setup(tspws_hip_plan *p, const tspws_band *bands, unsigned R, hipStream_t st)
+{
+	if (!p->bands) {
+		BandTables *t = new BandTables;
+		p->bands = t;
+		for (unsigned s = 0; s < p->S; s++) {
+			OctDesc o;
+			memset(&o, 0, sizeof o);
+			o.gen = p->sc[s].inv_fast ? 0u : 1u;
+			o.s0 = s; o.nv = 1; o.D = p->sc[s].D; o.Ns = p->sc[s].Ns;
+			unsigned dl = 1, lg = 0;
+			while (dl < o.D && dl < 64) { dl <<= 1; lg++; }
+			o.DL = dl; o.logDL = lg;
+			o.MC = o.D > 64 ? (o.D + 63) / 64 : 1;
+			const unsigned NG = (o.Ns + INV_R - 1) / INV_R, GW = 64 / o.DL;
+			o.ngw = (NG + GW - 1) / GW;
+			t->per_scale.push_back(o);
+		}
+		HIP_TRY(hipMalloc(&t->d_oc, std::max<size_t>(1, p->S) * sizeof(OctDesc)));
+		HIP_TRY(hipMalloc(&t->d_bt, TSPWS_MAX_BANDS * sizeof(BandSlots)));
+	}
+	BandTables &t = *p->bands;
+	if (t.valid && t.table.size() == R && (!R || !memcmp(t.table.data(), bands, R * sizeof(tspws_band)))) return 0;
+	t.valid = false;
+	std::vector<unsigned> rank(p->S + 1, 0); // scales with work items below s
+	{
+		std::vector<char> in(p->S, 0);
+		for (unsigned r = 0; r < R; r++)
+			for (unsigned s = bands[r].s_begin; s < bands[r].s_end; s++) in[s] = 1;
+		for (unsigned s = 0; s < p->S; s++) rank[s + 1] = rank[s] + (in[s] ? 1u : 0u);
+	}
+	std::vector<OctDesc> oc;
+	for (unsigned s = 0; s < p->S; s++)
+		if (rank[s + 1] > rank[s]) { oc.push_back(t.per_scale[s]); oc.back().slot = rank[s]; }
+	std::stable_sort(oc.begin(), oc.end(), [](const OctDesc &x, const OctDesc &y) { return x.gen < y.gen; });
+	unsigned woff = 0;
+	t.waves_fast = t.waves_lds = 0;
+	for (OctDesc &o : oc) {
+		o.wave_off = woff;
+		woff += o.MC * o.ngw;
+		if (!o.gen) t.waves_fast = woff;
+		if (!o.gen && o.D <= inv_lds_maxd() && t.waves_lds == o.wave_off) t.waves_lds = woff; // (the finely decimated scales come first, as in tspws_build_inverse)
+	}
+	if (const char *e = sweep_env("TSPWS_INV_LDS")) if (*e == '0') t.waves_lds = 0;
+	t.waves = woff; t.U = (unsigned)oc.size();
+	std::vector<BandSlots> bt(R);
+	for (unsigned r = 0; r < R; r++) { bt[r].slot0 = rank[bands[r].s_begin]; bt[r].n = bands[r].s_end - bands[r].s_begin; } // (every scale of a band has a row)
+	HIP_TRY(hipStreamSynchronize(st)); // an earlier call on this stream may still read the tables
+	if (!oc.empty()) HIP_TRY(hipMemcpy(t.d_oc, oc.data(), oc.size() * sizeof(OctDesc), hipMemcpyHostToDevice));
+	if (R) HIP_TRY(hipMemcpy(t.d_bt, bt.data(), R * sizeof(BandSlots), hipMemcpyHostToDevice));
+	t.table.assign(bands, bands + R);
+	t.valid = true;
+	return 0;
+}
+
+// the waves of the band table's list for nb groups of NREC sets (grid.y), as inv_launch_waves: the LDS-staged scales beside the others when there are both
+template <int NREC, bool QUAD>
+static int bands_launch_waves(tspws_hip_plan *p, const double2 *Y, unsigned nb, double *ob, size_t y_obuf, size_t q_off, hipStream_t st)
+{
+	const BandTables &t = *p->bands;
+	const size_t slot = (size_t)NREC * p->N, y_coef = (size_t)NREC * p->ncoef;
+	const unsigned wl = nb >= 2 ? t.waves_lds : 0u, wf = t.waves_fast, w1 = t.waves;
+	const bool beside = wl > 0 && wf > wl;
+	if (beside) if (int rc = tspws_fork(p, st, p->side, p->ev_fork)) return rc;
+	if (wl > 0)
+		hipLaunchKernelGGL((k_inv_poly<NREC, false, true, QUAD>), dim3((wl + 3) / 4, nb), dim3(256), 0, beside ? p->side : st, Y, p->ncoef, p->N, p->d_sc,
+		                   (const OctDesc *)t.d_oc, t.U, p->d_wd, ob, slot, wl, y_coef, y_obuf, 0u, q_off);
+	if (wf > wl)
+		hipLaunchKernelGGL((k_inv_poly<NREC, false, false, QUAD>), dim3((wf - wl + 3) / 4, nb), dim3(256), 0, st, Y, p->ncoef, p->N, p->d_sc, (const OctDesc *)t.d_oc,
+		                   t.U, p->d_wd, ob, slot, wf, y_coef, y_obuf, wl, q_off);
+	if (w1 > wf)
+		hipLaunchKernelGGL((k_inv_poly<NREC, true, false, QUAD>), dim3((w1 - wf + 3) / 4, nb), dim3(256), 0, st, Y, p->ncoef, p->N, p->d_sc, (const OctDesc *)t.d_oc,
+		                   t.U, p->d_wd, ob, slot, w1, y_coef, y_obuf, wf, q_off);
+	if (beside) return tspws_join(p->side, st, p->ev_join);
+	return 0;
+}
+
+int tspws_inverse_bands_run(tspws_hip_plan *p, const double2 *Y, size_t nset, const tspws_band *bands, unsigned R, const BandOut &out, hipStream_t st,
+                            unsigned *finish_batches, unsigned *scales)
+{
+	if (int rc = bands_setup(p, bands, R, st)) return rc;
+	const BandTables &t = *p->bands;
+	const bool f32 = out.ts != nullptr, quad = f32 ? out.ts_env != nullptr : out.im != nullptr;
+	const size_t N = p->N, UN = (size_t)t.U * N;
+	if (scales) *scales = t.U;
+	// sets per finish batch: their slot rows (U x N doubles per set, twice that with the quadrature) within the parts budget; even, so that
+	// the pairs are the same whatever the batching
+	const size_t per_set = std::max<size_t>(1, (quad ? 2 : 1) * UN) * sizeof(double);
+	const size_t batch = even_rows_per_batch(tspws_part_budget_bytes(), per_set, std::max<size_t>(nset, 2));
+	const unsigned nbx = (unsigned)((N + 255) / 256);
+	for (size_t j0 = 0; j0 < nset; j0 += batch) {
+		const unsigned ns = (unsigned)std::min(batch, nset - j0), pairs = quad ? 0u : ns / 2;
+		if (finish_batches) ++*finish_batches;
+		void *v;
+		if (int rc = scratch(p, SCR_OBUF, (size_t)ns * per_set, &v)) return rc;
+		double *ob = (double *)v;
+		const double2 *Yb = Y + j0 * p->ncoef;
+		if (t.waves) {
+			int rc = 0;
+			if (quad) rc = bands_launch_waves<1, true>(p, Yb, ns, ob, 2 * UN, UN, st);
+			else {
+				if (pairs) rc = bands_launch_waves<2, false>(p, Yb, pairs, ob, 2 * UN, 0, st);
+				if (!rc && (ns & 1)) rc = bands_launch_waves<1, false>(p, Yb + (size_t)(ns - 1) * p->ncoef, 1, ob + (size_t)pairs * 2 * UN, UN, 0, st);
+			}
+			if (rc) return rc;
+		}
+		BandCombine a;
+		a.N = N; a.U = t.U; a.paired = 2 * pairs; a.set0 = (unsigned)j0; a.quad = quad ? 1u : 0u;
+		a.bt = t.d_bt;
+		a.re = out.re; a.im = out.im;
+		a.ts = out.ts; a.ls = out.ls; a.ts_env = out.ts_env; a.ls_env = out.ls_env;
+		a.row = out.d_row; a.cnt = out.d_cnt; a.row0 = out.row0; a.cnt0 = out.cnt0;
+		if (f32) hipLaunchKernelGGL(k_inv_combine_bands<true>, dim3(nbx, R, ns), dim3(256), 0, st, (const double *)ob, a);
+		else hipLaunchKernelGGL(k_inv_combine_bands<false>, dim3(nbx, R, ns), dim3(256), 0, st, (const double *)ob, a);
+	}
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+extern "C" int tspws_hip_inverse_bands(tspws_hip_plan *p, const double *d_Y, size_t nset, const tspws_band *h_bands, unsigned R, double *d_re, double *d_im,
+                                       void *s)
+{
+	if (int rc = tspws_bands_check(p, h_bands, R, "inverse_bands")) return rc;
+	if (!p) return fail(TSPWS_E_ARG, "inverse_bands: NULL");
+	if (!R || !nset) return 0;
+	if (!d_Y || !h_bands || !d_re) return fail(TSPWS_E_ARG, "inverse_bands: NULL");
+	HIP_TRY(hipSetDevice(p->device));
+	BandOut out;
+	out.re = d_re; out.im = d_im;
+	return tspws_inverse_bands_run(p, (const double2 *)d_Y, nset, h_bands, R, out, S_(s), nullptr, nullptr);
+}
+
+extern "C" int tspws_bands_from_frequencies(const double *scale, unsigned S, double w0, double dt, const double *f_lo, const double *f_hi, unsigned R,
+                                            tspws_band *bands, double *fc)
+{
+	if (!scale && S) return fail(TSPWS_E_ARG, "bands_from_frequencies: NULL");
+	if (R && (!f_lo || !f_hi || !bands)) return fail(TSPWS_E_ARG, "bands_from_frequencies: NULL");
+	if (!(dt > 0) || !std::isfinite(dt)) return fail(TSPWS_E_ARG, "bands_from_frequencies: dt must be positive");
+	for (unsigned r = 0; r < R; r++) {
+		if (!std::isfinite(f_lo[r]) || !std::isfinite(f_hi[r])) return fail(TSPWS_E_ARG, "bands_from_frequencies: a band edge is not finite");
+		if (f_lo[r] > f_hi[r]) return fail(TSPWS_E_ARG, "bands_from_frequencies: f_lo > f_hi");
+	}
+	auto centre = [&](unsigned s) { return w0 / (2 * TSPWS_PI * dt * scale[s]); }; // ts_pws1f_lib.c:112
+	if (fc) for (unsigned s = 0; s < S; s++) fc[s] = centre(s);
+	for (unsigned r = 0; r < R; r++) {
+		// fc decreases with s: [first s with fc_s < f_hi, first s with fc_s < f_lo)
+		unsigned a = 0, b;
+		while (a < S && !(centre(a) < f_hi[r])) a++;
+		b = a;
+		while (b < S && !(centre(b) < f_lo[r])) b++;
+		bands[r].s_begin = a; bands[r].s_end = b;
+	}
 	return 0;
 }
 

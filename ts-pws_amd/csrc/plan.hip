@@ -270,6 +270,7 @@ extern "C" void tspws_hip_plan_destroy(tspws_hip_plan *p)
 	for (hipEvent_t e : {p->ck_ev, p->ev_fork, p->ev_join, p->ev_xs0, p->ev_xs1, p->ev_xs2, p->ev_mid, p->ev_lin}) if (e) (void)hipEventDestroy(e);
 	for (hipStream_t st : {p->side, p->xs, p->xf}) if (st) (void)hipStreamDestroy(st);
 	if (p->d_oc) (void)hipFree(p->d_oc);
+	tspws_bands_destroy(p);
 	tspws_spectral_destroy(p);
 	for (TlTable &T : p->tl) { if (T.d_sc) (void)hipFree(T.d_sc); if (T.d_items) (void)hipFree(T.d_items); }
 	if (p->d_sc) (void)hipFree(p->d_sc);

@@ -5,12 +5,12 @@
 //   plan.hip      parameters, frame geometry, tap generation, runtime helpers, synthetic traces
 //   stream.hip    trace prologue + stage 1: the HBM-streaming partial-stack pass
 //   forward.hip   forward frame CWT (fwd_lds.h, fwd_poly.h, fwd_tl.h) + linear / phase stacks
-//   inverse.hip   phase weighting, inverse frame CWT (inv_poly.h), epilogue
+//   inverse.hip   phase weighting, inverse frame CWT (inv_poly.h), epilogue; the band rows (per-scale work list, quadrature, combining kernel)
 //   stack.hip     the whole call on device-resident traces: local half, finish stage (whole / in pieces / by scales)
 //   resample.hip  jackknife, random subsampling, convergence curves
 //   spectral.hip  the far-decimated octaves through the traces' spectra (spectral.h)
 //   jk_single.hip single-stage jackknife from per-class stacks
-//   batch.hip     many same-length ensembles in one call
+//   batch.hip     many same-length ensembles in one call, with the plain or the band-limited finish
 //   jk_batch.hip  single-stage jackknife of many ensembles in one call
 //   jk_batch_two_stage.hip  two-stage jackknife of many ensembles in one call
 //   conv_batch.hip  convergence curves of many ensembles in one call
@@ -240,6 +240,7 @@ struct tspws_hip_plan {
 	unsigned inv_waves_lds = 0; // ... of which the first inv_waves_lds (octaves with D < 64) run the LDS-staged instantiation
 	unsigned inv_waves = 0, inv_waves_fast = 0, inv_noct = 0, inv_ngeneric = 0; // polyphase inverse: waves (of the octaves whose D divides N first), octave items, scales left to the generic kernel
 	OctDesc *d_oc = nullptr;
+	struct BandTables *bands = nullptr; // band rows (inverse.hip): the per-scale work list, built at the first band call, and the device copy of the band table in force
 	std::vector<ScaleDesc> sc;
 	ScaleDesc *d_sc = nullptr;
 	double2 *d_w = nullptr, *d_wd = nullptr;
@@ -292,6 +293,7 @@ struct tspws_hip_plan {
 	tspws_hip_boot_batch_stats boot_batch_stats{}; // ... and the last batched bootstrap (boot_batch.hip)
 	tspws_hip_weighted_batch_stats weighted_batch_stats{}; // ... and the last batched weighted stack (weighted_batch.hip)
 	tspws_hip_bands_stats bands_stats{}; // ... and the last percentile bands (replica_bands.hip)
+	tspws_hip_stack_bands_stats stack_bands_stats{}; // ... and the last band-limited batched stack (batch.hip)
 	tspws_hip_trace_scores_stats_t trace_scores_stats{}; // ... and the last trace scores (trace_scores.hip)
 };
 
@@ -453,6 +455,20 @@ int  tspws_inverse_scales(tspws_hip_plan *p, const double2 *Y, double *x2, hipSt
 int  tspws_inverse_pairs_early(tspws_hip_plan *p, const double2 *Y, unsigned nb, unsigned s_split, hipStream_t early, bool *done);
 int  tspws_inverse_pairs_late(tspws_hip_plan *p, const double2 *Y, double *x, unsigned nb, unsigned s_split, hipStream_t st);
 bool tspws_generic_inverse();
+// band rows of nset coefficient sets (tspws_hip_inverse_bands' definitions; the table is checked by the caller: tspws_bands_check), in finish
+// batches within the parts budget.  Either the FP64 rows re / im ([nset][R][N]; im NULL: no quadrature), or -- ts != NULL -- the batched stack's
+// floats: sets 2k / 2k + 1 = (OUT, ST) of stack k, whose output row [.][R][N] and trace count are d_row[k] / d_cnt[k] (d_row NULL: row0 + k, cnt0);
+// ts_env / ls_env both NULL (no quadrature) or both given.
+struct BandOut {
+	double *re = nullptr, *im = nullptr;
+	float *ts = nullptr, *ls = nullptr, *ts_env = nullptr, *ls_env = nullptr;
+	const unsigned *d_row = nullptr, *d_cnt = nullptr;
+	unsigned row0 = 0, cnt0 = 1;
+};
+int  tspws_bands_check(const tspws_hip_plan *p, const tspws_band *bands, unsigned R, const char *who);
+int  tspws_inverse_bands_run(tspws_hip_plan *p, const double2 *Y, size_t nset, const tspws_band *bands, unsigned R, const BandOut &out, hipStream_t st,
+                             unsigned *finish_batches, unsigned *scales);
+void tspws_bands_destroy(tspws_hip_plan *p);
 // ts rows: (float) x[j][n] for nb rows (replica outputs)
 void tspws_epilogue_rows(float *d_ts, const double *d_x, size_t N, unsigned nb, hipStream_t st);
 // stream.hip
