@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Bit-for-bit comparison of the batched entry points between two builds of the library: the parent's (ts-pws_amd/lib/variant_base.so, from
 tools/build_base.sh) and the working tree's.  For each library and for TSPWS_PART_MB unset and = 16 a fresh child process (library by
-TSPWS_LIB_PATH) runs the seven entry points -- stack_batch, jackknife_single, jackknife_batch, jackknife_batch_two_stage, convergence_batch,
-subsample_batch_sel (masks given) and subsample_batch (masks drawn after srand) -- on seeded inputs and stores every float output and count; the parent process compares the stored arrays
-byte for byte and exits non-zero on any difference.
+TSPWS_LIB_PATH) runs the nine entry points -- stack_batch, jackknife_single, jackknife_batch, jackknife_batch_two_stage, convergence_batch,
+subsample_batch_sel (masks given), subsample_batch (masks drawn after srand), bootstrap_batch (counts given, with the statistics) and
+weighted_stack_batch -- on seeded inputs and stores every float output, count and Keff; the parent process compares the stored arrays byte
+for byte and exits non-zero on any difference.
 
 Shapes: 13 ensembles of 0-70 traces (one empty, one of 70 that straddles a 64-trace block, one of exactly 64), N = 4096 and N = 4001; the
 single-stage parameter set and Kmax = 10, unbiased; 9 jackknife columns for the single-stage jackknives, 17 columns / masks (two column tiles
-of the two-stage walk, three mask groups) for the others.  A child fails unless the stats calls say that the shared paths ran.
+of the two-stage walk, three groups of 8 rows, the last holding one) for the others.  The count matrix: an all-zero row, a 0/1 row, one entry
+of 255, otherwise 0..3; the weight matrix: an all-zero row, a row with a single weight, a 0/1 row, a row spanning 1e-6..1e6, otherwise
+uniform in [0, 1).  A child fails unless the stats calls say that the shared paths ran (with the 16 MB budget: in more than one round).
 usage: batch_ab.py [base.so new.so]      (child: batch_ab.py run out.npz)"""
 import ctypes as C
 import importlib
@@ -39,11 +42,29 @@ def bins_selection(sizes, C):
     return sel
 
 
+def row_matrices(seed):
+    """[C2][T] bootstrap counts and weights over the traces of SIZES_MIXED (docstring above)"""
+    rng = np.random.default_rng(seed)
+    T = sum(SIZES_MIXED)
+    cnt = rng.integers(0, 4, (C2, T)).astype(np.uint8)
+    cnt[0] = 0
+    cnt[1] = rng.integers(0, 2, T)
+    cnt[2, 7] = 255
+    w = rng.random((C2, T))
+    w[0] = 0
+    w[1] = 0
+    w[1, 40] = 0.75
+    w[2] = rng.integers(0, 2, T)
+    w[3] = 10.0 ** rng.uniform(-6, 6, T)
+    return cnt, w
+
+
 def child(path):
     import torch
     import abi
     tspws = importlib.import_module("ts-pws_amd")
     out = {}
+    small = "TSPWS_PART_MB" in os.environ  # the budget that forces several rounds
 
     def keep(tag, *arrays):
         for k, a in enumerate(arrays):
@@ -92,6 +113,15 @@ def child(path):
             st = pl.subsample_batch_stats()
             assert st["single_shared"] == n1 and st["two_stage_shared"] == n2 and st["looped"] == 0, st
             if not two:
+                assert st["rounds"] > 1 or not small, st  # (every ensemble single-stage: the rounds are those of the row batches)
+                # bootstrap_batch (counts given, with the statistics) and weighted_stack_batch: the other two row batches
+                cnt, w = row_matrices(N + 1)
+                keep(tag + ".boot", *pl.bootstrap_batch(X, first_m, cnt, stats=True))
+                st = pl.bootstrap_batch_stats()
+                assert st["shared"] == n1 > 0 and st["empty"] == 1 and st["max_count"] == 255 and (st["rounds"] > 1 or not small), st
+                keep(tag + ".weighted", *pl.weighted_stack_batch(X, first_m, w))
+                st = pl.weighted_stack_batch_stats()
+                assert st["shared"] == n1 > 0 and st["empty"] == 1 and (st["rounds"] > 1 or not small), st
                 sel = bins_selection(SIZES_MIXED, C1)
                 keep(tag + ".jkb", *pl.jackknife_batch(X, first_m, sel))
                 st = pl.jackknife_batch_stats()

@@ -11,7 +11,7 @@ mean, min and max of 3 calls per route after one warm-up call each.  Every outpu
 worst relerr of any row between the two calls is printed (biased weights: the two estimators agree to rounding).
 usage: weighted_batch_bench.py
 weighted_batch_bench.py --profile: ONE call of each kind on 8 x (499 x 16501), M = 100, after one warm-up call each (under rocprofv3
---kernel-trace --stats: the times of k_wb_accumulate and k_bt_accumulate side by side).
+--kernel-trace --stats: the times of k_rb_accumulate<WeightRows> and k_rb_accumulate<CountRows> side by side).
 """
 import importlib
 import json

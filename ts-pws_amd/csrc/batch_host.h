@@ -1,6 +1,7 @@
 // batch_host.h -- host code that the batched entry points share (batch.hip, jk_single.hip, jk_batch.hip, jk_batch_two_stage.hip, conv_batch.hip,
 // sub_batch.hip, boot_batch.hip, weighted_batch.hip): the lifetime of a call's uploads, the layout of a table block, the planning of rounds and finish batches, and the small loops
-// over a selection that every unit needs.  Only what removes knowledge from its call sites lives here; the kernels they share are in batch_kernels.h.
+// over a selection that every unit needs.  Only what removes knowledge from its call sites lives here; the kernels they share are in batch_kernels.h,
+// and what sub_batch.hip, boot_batch.hip and weighted_batch.hip share beyond that -- their kernels, round driver and argument check -- in row_batch.h.
 #pragma once
 
 #include "tspws_internal.h"

@@ -1,7 +1,8 @@
 // batch_kernels.h -- small kernels that the batched entry points share: the gather of batch.hip and jk_batch.hip, the class time sums and the
-// replicas' finish (weighted sets, linear stacks) of jk_single.hip and jk_batch.hip, the per-row weight mode of those and sub_batch.hip, the
-// rows' finish (weighted sets, float epilogue) of sub_batch.hip and boot_batch.hip (the epilogue also of weighted_batch.hip).  Every
-// unit that includes this header gets its own copy (internal linkage: the units are compiled without relocatable device code).
+// replicas' finish (weighted sets, linear stacks) of jk_single.hip and jk_batch.hip, the per-row weight mode of those and of the row batches,
+// the rows' finish (weighted sets, float epilogue) of the row batches (sub_batch.hip, boot_batch.hip; the epilogue also of weighted_batch.hip),
+// whose own kernels -- the accumulation and the linear stack, templates over the row's code -- are in row_batch.h.  Every unit that includes
+// this header gets its own copy (internal linkage: the units are compiled without relocatable device code).
 #pragma once
 
 #include "tspws_internal.h"
@@ -105,10 +106,10 @@ template <bool LDS>
 	out[((size_t)e.row * C + c) * N + n] = K ? (float)(acc * (1.0 / (double)K)) : 0.f;
 }
 
-// A single-stage ensemble of a round of sub_batch.hip / boot_batch.hip / weighted_batch.hip: first trace, its selection table, traces, index of its first trace in
-// the round's partials, output block.  The table of group g of 8 rows holds one entry per trace j at [bits_off + g m + j]: sub_batch.hip a
-// byte with the 8 mask bits, boot_batch.hip an aligned 8-byte word with the 8 count bytes, weighted_batch.hip an aligned 64-byte block with
-// the 8 FP64 weights.
+// A single-stage ensemble of a round of row_batch.h: first trace, its codes in the round's table, traces, index of its first trace in the
+// round's partials, output block.  The codes of group g of 8 rows hold one entry per trace j at [bits_off + g m + j]: sub_batch.hip a byte
+// with the 8 mask bits, boot_batch.hip an aligned 8-byte word with the 8 count bytes, weighted_batch.hip an aligned 64-byte block with the
+// 8 FP64 weights.
 struct SbEns { unsigned long long t0, bits_off; unsigned m, part0, row, pad; };
 
 // weighted coefficients of the rows r0 + blockIdx.y of the round: OUT = ST * weight(PS; K = M = K_r), the mode by the row's own K (K = 1: the
