@@ -1,6 +1,6 @@
 // batch_host.h -- host code that the batched entry points share (batch.hip, jk_single.hip, jk_batch.hip, jk_batch_two_stage.hip, conv_batch.hip,
-// sub_batch.hip, boot_batch.hip, weighted_batch.hip): the lifetime of a call's uploads, the layout of a table block, the planning of rounds and finish batches, and the small loops
-// over a selection that every unit needs.  Only what removes knowledge from its call sites lives here; the kernels they share are in batch_kernels.h,
+// sub_batch.hip, boot_batch.hip, weighted_batch.hip): the lifetime of a call's uploads, the planning of rounds and finish batches, and the small loops
+// over a selection that every unit needs (the layout of a table block, TableLayout, is in column_runs.h).  Only what removes knowledge from its call sites lives here; the kernels they share are in batch_kernels.h,
 // and what sub_batch.hip, boot_batch.hip and weighted_batch.hip share beyond that -- their kernels, round driver and argument check -- in row_batch.h.
 #pragma once
 
@@ -36,20 +36,6 @@ private:
 	hipStream_t st_;
 	bool drained_ = false;
 	std::deque<std::vector<char>> blocks_;
-};
-
-// The layout of a table block: the arrays one after the other, each aligned for its element type.  A unit states its block ONCE, as a function of
-// the arrays' lengths; with upper bounds of the lengths the same function gives an upper bound of the block (add is monotone in count, whatever
-// came before), which is what plans the rounds.
-struct TableLayout {
-	size_t bytes = 0;
-	template <class T>
-	size_t add(size_t count) // offset of an array of `count` T
-	{
-		const size_t o = (bytes + alignof(T) - 1) / alignof(T) * alignof(T);
-		bytes = o + count * sizeof(T);
-		return o;
-	}
 };
 
 // Rows of one finish batch: sets, reconstructions and the inverse's octave buffer of the batch within `budget` at per_row bytes a row

@@ -6,8 +6,8 @@
 // per ensemble a new selection for the masked-replica tables (resample.hip keeps ONE per host thread), an upload, a wait, and a handful of
 // 5-40 us launches on ~130 rows.  This unit does the whole batch at once:
 //   host      ONE pass over the selection: per ensemble and column (replica; the plain stack as column C) the piecewise-constant group
-//             signature exactly as masked_plan builds it (integer quotient k Kmax / max(K_c, 1), deleted stretches by memchr, plain-stack
-//             steps at ceil(g M_b / Kmax)); the columns in tiles of <= 16, the traces of an (ensemble, tile) cut into runs of one signature
+//             signature -- the rule and the builders the masked replicas of a single ensemble use too (column_runs.h); the columns in tiles
+//             of <= 16, the traces of an (ensemble, tile) cut into runs of one signature
 //   walk      k_jb2_rows_walk: a workgroup owns one (ensemble, tile, 1024 samples), walks the ensemble's traces once in trace order with a
 //             running FP64 sum per column in registers (16 columns x 4 samples per lane); at the end of a run the run's sum goes to the
 //             columns it belongs to (wave-uniform bit tests), and a column whose group ends there stores its sum as that group's row and
@@ -30,7 +30,6 @@ namespace {
 
 constexpr unsigned J2_W = 16;          // columns per tile: running sums a lane keeps in registers (16 x 4 doubles)
 constexpr int J2_NL = 8;               // independent row loads in flight per lane
-constexpr unsigned J2_DELETED = ~0u;   // signature of a trace that a replica does not keep
 
 struct J2Wg { unsigned run0, run1; };  // the runs of one (ensemble, tile) in the round's run list
 
@@ -181,58 +180,6 @@ __global__ void __launch_bounds__(256) k_jb2_epilogue(const double *__restrict__
 
 namespace {
 
-struct Piece { size_t pos; unsigned v; }; // a column has signature v from trace pos on (local index), up to the next piece
-
-// The pieces of one column of an ensemble of m traces, as masked_plan (resample.hip) builds them.  row != NULL: a replica, row[i] == 1 =
-// trace i is kept -- its signature changes where the selection byte changes and, inside a stretch of kept traces, where floor(k KM / K_c)
-// steps (k = rank among the kept traces, :766; the integer quotient is the reference's floor of the double quotient); returns K_c.  row ==
-// NULL: the plain stack, min(floor(i KM / m), KM - 1), steps at ceil(g m / KM).
-size_t column_pieces(const unsigned char *row, size_t m, unsigned KM, std::vector<Piece> &pc)
-{
-	pc.clear();
-	auto emit = [&](size_t pos, unsigned v) {
-		if (!pc.empty() && pc.back().v == v) return; // (no change after all)
-		pc.push_back(Piece{pos, v});
-	};
-	if (!row) {
-		emit(0, 0);
-		for (unsigned long long g = 1; g < KM; g++) {
-			const unsigned long long pos = (g * m + KM - 1) / KM;
-			if (pos >= m) break;
-			emit((size_t)pos, (unsigned)(pos * KM / m));
-		}
-		return m;
-	}
-	size_t n = 0;
-	for (size_t i = 0; i < m; i++) n += row[i] == 1;
-	const unsigned long long Kc = std::max<size_t>(n, 1);
-	unsigned long long k = 0, g = 0, kb = (Kc + KM - 1) / KM; // rank among the kept traces; its group; the rank at which the group steps next
-	size_t i = 0;
-	if (m && row[0] != 1) emit(0, J2_DELETED);
-	while (i < m) {
-		if (row[i] != 1) { // a stretch that is not kept: up to the next byte 1
-			const void *q = memchr(row + i, 1, m - i);
-			i = q ? (size_t)((const unsigned char *)q - row) : m;
-			continue;
-		}
-		size_t j = i; // a stretch of kept traces [i, j)
-		while (j + 8 <= m) { unsigned long long w; memcpy(&w, row + j, 8); if (w != 0x0101010101010101ull) break; j += 8; }
-		while (j < m && row[j] == 1) j++;
-		const unsigned long long k1 = k + (j - i);
-		if (kb <= k) { g = k * KM / Kc; kb = ((g + 1) * Kc + KM - 1) / KM; }
-		emit(i, (unsigned)g);
-		while (kb < k1) { // the group steps inside the stretch
-			const size_t pos = i + (size_t)(kb - k);
-			g = kb * KM / Kc; kb = ((g + 1) * Kc + KM - 1) / KM;
-			emit(pos, (unsigned)g);
-		}
-		k = k1;
-		if (j < m) emit(j, J2_DELETED);
-		i = j;
-	}
-	return n;
-}
-
 struct Ens { unsigned b; size_t f, m; bool unwritten; }; // ensemble with traces: index, first trace, traces; some row of it is never stored
 
 // tables of the whole call: runs and flush destinations of every (ensemble, tile), in that order
@@ -244,63 +191,13 @@ struct Tables {
 	std::vector<size_t> flush_ptr;  // flush destinations of ensemble j: [flush_ptr[j], flush_ptr[j + 1])
 };
 
-// runs, column bits and flush destinations of columns [c0, c1) (of W = C [+ 1]) of one ensemble
+// runs, column bits and flush destinations of columns [c0, c1) (of W = C [+ 1]) of one ensemble, by the shared rule (column_runs.h)
 void build_tile(const char *h_sel, size_t Tn, size_t col0, const Ens &e, unsigned KM, unsigned C, unsigned c0, unsigned c1, unsigned *Kc_out, Tables &T,
                 bool &unwritten)
 {
-	static thread_local std::vector<Piece> pieces[J2_W];
-	static thread_local std::vector<unsigned char> chg; // chg[i]: trace i starts a run
-	static thread_local std::vector<unsigned> sig;
-	const size_t m = e.m;
-	chg.assign(m + 1, 0);
-	chg[0] = 1;
-	for (unsigned c = c0; c < c1; c++) {
-		std::vector<Piece> &pc = pieces[c - c0];
-		const size_t n = column_pieces(c < C ? (const unsigned char *)h_sel + (size_t)c * Tn + col0 : nullptr, m, KM, pc);
-		if (c < C) Kc_out[c] = (unsigned)n;
-		for (const Piece &q : pc) chg[q.pos] = 1;
-	}
-	const size_t run0 = T.runs.size();
-	for (size_t i = 0; i < m;) {
-		size_t j = i + 1;
-		if (j < m) {
-			const void *q = memchr(chg.data() + j, 1, m - j);
-			j = q ? (size_t)((const unsigned char *)q - chg.data()) : m;
-		}
-		RunDesc d;
-		memset(&d, 0, sizeof d);
-		d.t0 = e.f + i; d.count = (unsigned)(j - i);
-		T.runs.push_back(d);
-		i = j;
-	}
-	const size_t nr = T.runs.size() - run0;
-	RunDesc *R = T.runs.data() + run0;
-	sig.resize((size_t)(c1 - c0) * nr);
-	for (unsigned c = c0; c < c1; c++) {
-		const std::vector<Piece> &pc = pieces[c - c0];
-		unsigned *sg = sig.data() + (size_t)(c - c0) * nr;
-		size_t q = 0;
-		for (size_t r = 0; r < nr; r++) { // group of run r in the column: the piece that holds the run's first trace
-			const size_t t = (size_t)(R[r].t0 - e.f);
-			while (q + 1 < pc.size() && pc[q + 1].pos <= t) q++;
-			sg[r] = pc.empty() ? J2_DELETED : pc[q].v;
-		}
-		// from the last run back: a run that belongs to the column ends the column's group when the next run that belongs to it has another group
-		unsigned next_g = J2_DELETED, stored = 0;
-		for (size_t r = nr; r-- > 0;) {
-			const unsigned g = sg[r];
-			if (g == J2_DELETED) continue;
-			R[r].member |= 1u << (c - c0);
-			if (g != next_g) { R[r].flush |= 1u << (c - c0); stored++; }
-			next_g = g;
-		}
-		if (stored < KM) unwritten = true;
-	}
-	for (size_t r = 0; r < nr; r++) { // flush destinations in ascending column order
-		R[r].frow = (unsigned)T.flush.size();
-		for (unsigned c = c0; c < c1; c++)
-			if ((R[r].flush >> (c - c0)) & 1u) T.flush.push_back(c * KM + std::min(sig[(size_t)(c - c0) * nr + r], KM - 1));
-	}
+	static thread_local ColumnWork work;
+	auto sel = [&](unsigned c) { return c < C ? (const unsigned char *)h_sel + (size_t)c * Tn + col0 : nullptr; };
+	if (tile_runs(work, e.m, KM, c0, c1, sel, [&](unsigned g, unsigned c) { return c * KM + g; }, e.f, Kc_out, T.runs, T.flush)) unwritten = true;
 }
 
 // the tables of a round in one block: trace counts of the nsl slices (doubles) | runs | (ensemble, tile) run ranges | flush rows | counts | output rows

@@ -1,6 +1,7 @@
 // resample.hip -- jackknife (two-stage), random subsampling, convergence curves.
 // Reference citations are relative to /root/reference/src.
 #include "tspws_internal.h"
+#include "masked_tables.h"
 #include <atomic>
 #include <chrono>
 #include <string>
@@ -61,7 +62,6 @@ __global__ void __launch_bounds__(256) k_jk_linear(const double *__restrict__ P,
 	out[n] = (float)(acc * invK);
 }
 
-static constexpr unsigned SIG_DELETED = ~0u; // (32-bit signatures: Kmax is an unsigned in t_tsPWS, any value is a legal group count)
 
 // (host tables handed to asynchronous copies: the call synchronises its stream before they can change)
 static int cs_done(hipStream_t st) { HIP_TRY(hipStreamSynchronize(st)); return 0; }
@@ -162,42 +162,7 @@ static int finish_replicas(tspws_hip_plan *pl, const t_tsPWS *p, double *d_P, co
 // selection (per host thread, keyed by content) AND stays on the device while the plan's table block is not reused
 // (plan->jk_gen): a repeated selection issues no host-to-device copy at all.
 // ------------------------------------------------------------------------------------------
-struct MaskedPlan {
-	// key
-	size_t mtr = 0, N = 0, first = 0, mtr_local = 0;
-	unsigned C = 0, KM = 0, gps = 0;
-	bool with_main = false, valid = false, allow_direct = true;
-	std::vector<char> sel;
-	// products
-	unsigned long long gen = 0;
-	unsigned W = 0, nstage = 0;
-	std::vector<size_t> Kc;
-	std::vector<Chunk> runs;            // maximal runs of consecutive traces with one signature (cut at the stage ends), trace order
-	std::vector<unsigned> seg_first;    // per stage: the first runs of its segments + the end (nseg + 1 entries), stages concatenated
-	std::vector<unsigned> stage_seg0;   // per stage: its first entry in seg_first (nstage + 1)
-	std::vector<unsigned> carry;        // per stage: snapshots whose sum is the prefix sum at the stage's start
-	std::vector<unsigned> carry_ptr;    // (nstage + 1)
-	std::vector<unsigned> trow_ptr;     // rows as signed sums of snapshots: [KM W + 1] pointers, rows in stage / column / group order
-	std::vector<unsigned> tidx;
-	std::vector<float> tcoef;
-	// few columns (W <= tspws_rows_walk_wmax()): the rows straight from the walk -- per run the columns it belongs to and the columns
-	// whose group ends with it (+ the rows those sums become)
-	bool direct = false, unwritten = false; // unwritten: some row is never stored (an empty group): the row block is cleared first
-	std::vector<RunDesc> rdesc;         // the runs with their column bits
-	std::vector<unsigned> stage_run0;   // per stage: its first run (nstage + 1)
-	std::vector<unsigned> stage_mid;    // per stage: first run of its second segment (== the next stage's first run: one segment)
-	std::vector<unsigned> fix_row;      // [nstage][W]: the first row column c stores in the stage's second segment (~0u: none)
-	std::vector<unsigned> flush_rows;   // flush destinations (RunDesc::frow points here)
-	std::vector<unsigned> rowmap;       // [W][KM]: row of (column, group)
-	std::vector<double> Mv;             // trace count per column (replicas: selected traces; plain stack: mtr)
-	std::vector<char> blob;             // all device tables in one block, offsets below
-	size_t o_mv = 0, o_rd = 0, o_tp = 0, o_ti = 0, o_tc = 0, o_map = 0, o_seg = 0, o_car = 0, o_fr = 0, o_fx = 0;
-	unsigned row_of(unsigned g, unsigned c) const
-	{
-		const unsigned g0 = g / gps * gps, ng = std::min(gps, KM - g0);
-		return g0 * W + c * ng + (g - g0);
-	}
-};
+// MaskedPlan itself, and the steps that build one: masked_tables.h
 
 static unsigned long long next_masked_gen()
 {
@@ -206,11 +171,14 @@ static unsigned long long next_masked_gen()
 }
 
 // Trace shards: the signatures come from the WHOLE selection (a trace's group in a replica is its rank among all selected traces, :766),
-// the runs cover the shard's traces [first, first + mtr_local) only, with trace indices local to the shard.
+// the runs cover the shard's traces [first, first + mtr_local) only, with trace indices local to the shard.  The tables themselves:
+// masked_build (masked_tables.h), from the columns' pieces (column_runs.h: a new selection of cfg4 -- 10 replicas x 10 000 traces, ~330 runs --
+// costs the host 0.04-0.06 ms, profiles/column_runs_refactor_ab.txt; TSPWS_JK_HOSTTIME=1 prints it per rebuild).
 static const MaskedPlan &masked_plan(size_t N, size_t mtr, const char *h_sel, unsigned C, unsigned KM, bool with_main, unsigned gps, bool allow_direct,
                                      size_t first, size_t mtr_local)
 {
 	static thread_local MaskedPlan mp;
+	static thread_local MaskedWork work;
 	if (mp.valid && mp.mtr == mtr && mp.N == N && mp.C == C && mp.KM == KM && mp.gps == gps && mp.with_main == with_main && mp.allow_direct == allow_direct && mp.first == first && mp.mtr_local == mtr_local &&
 	    mp.sel.size() == (size_t)C * mtr && !memcmp(mp.sel.data(), h_sel, (size_t)C * mtr)) return mp;
 	mp.valid = false;
@@ -218,278 +186,12 @@ static const MaskedPlan &masked_plan(size_t N, size_t mtr, const char *h_sel, un
 		std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 		~HostTimer() { static const bool on = sweep_env("TSPWS_JK_HOSTTIME") != nullptr; if (on) printf("masked_plan: %.1f us of host work\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count()); }
 	} host_timer;
-	const unsigned W = C + (with_main ? 1u : 0u);
-	mp.KM = KM; mp.gps = gps; mp.W = W;
-	const unsigned nstage = (KM + gps - 1) / gps;
-	// Signature of trace i: its group in every column (SIG_DELETED: not in that replica), COLUMN-major: one sequential pass per
-	// column that also marks where a run ends (chg) and where each group of the column ends (for the stage ends).  The reference's
-	// floor((double)(k * KM) / (double)Kc) (:766) is the integer quotient (k KM < 2^53 and a non-integer quotient is at least 1 / Kc away from the next integer), kept incrementally -- a 64-bit division
-	// per trace and column was a third of the 0.3 ms a new selection cost the host.
-	// Round 5: the columns as PIECES, not trace by trace.  A column's signature is piecewise constant: a replica's changes where its
-	// selection byte changes and, inside a stretch of selected traces, where floor(k KM / Kc) steps (k = rank among the selected traces);
-	// the plain stack's at ceil(g mtr / KM).  The stretches are found a machine word at a time, the group steps by ONE division per step
-	// (<= KM per column), and only the pieces' starts are written anywhere: a new selection of cfg4 (10 replicas x 10 000 traces,
-	// ~330 runs) costs the host ~0.03 ms instead of 0.16 (one pass per trace and column with a signature array of W x mtr words).
-	mp.Kc.assign(C, 0);
-	struct Piece { size_t pos; unsigned v; }; // the column has signature v from trace pos on (global index), up to the next piece
-	static thread_local std::vector<std::vector<Piece>> pieces;
-	static thread_local std::vector<unsigned char> chg; // chg[i]: trace i starts a run
-	pieces.resize(W);
-	chg.assign(mtr + 1, 0);
-	const size_t lo = first, hi = first + mtr_local; // the shard
-	if (lo < hi) chg[lo] = 1;
-	std::vector<size_t> T(nstage, 0); // end of stage s: one past the last trace that belongs to a group of stage <= s in any column
-	auto close_piece = [&](const Piece &pc, size_t end) { // [pc.pos, end) with one signature: stage ends inside the shard
-		if (pc.v == SIG_DELETED || end <= lo || pc.pos >= hi) return;
-		size_t &te = T[std::min(pc.v, KM - 1) / gps];
-		const size_t e = std::min(end, hi) - lo;
-		if (e > te) te = e;
-	};
-	for (unsigned c = 0; c < W; c++) {
-		std::vector<Piece> &pc = pieces[c];
-		pc.clear();
-		auto emit = [&](size_t pos, unsigned v) {
-			if (!pc.empty()) {
-				if (pc.back().v == v) return;               // (no change after all)
-				close_piece(pc.back(), pos);
-			}
-			pc.push_back(Piece{pos, v});
-			if (pos) chg[pos] = 1;
-		};
-		if (c < C) {
-			const unsigned char *row = (const unsigned char *)h_sel + (size_t)c * mtr;
-			size_t n = 0;
-			for (size_t i = 0; i < mtr; i++) n += row[i] == 1; // (vectorised)
-			mp.Kc[c] = n;
-			const unsigned long long Kc = std::max<size_t>(n, 1);
-			unsigned long long k = 0, g = 0, kb = (Kc + KM - 1) / KM; // rank among the selected traces; its group; the rank at which the group steps next
-			size_t i = 0;
-			if (mtr && row[0] != 1) emit(0, SIG_DELETED);
-			while (i < mtr) {
-				if (row[i] != 1) { // a stretch that is not selected: up to the next byte 1
-					const void *q = memchr(row + i, 1, mtr - i);
-					i = q ? (size_t)((const unsigned char *)q - row) : mtr;
-					continue;
-				}
-				size_t j = i; // a stretch of selected traces [i, j): words of eight bytes 1, then the tail
-				while (j + 8 <= mtr) { unsigned long long w; memcpy(&w, row + j, 8); if (w != 0x0101010101010101ull) break; j += 8; }
-				while (j < mtr && row[j] == 1) j++;
-				const unsigned long long k1 = k + (j - i);
-				if (kb <= k) { g = k * KM / Kc; kb = ((g + 1) * Kc + KM - 1) / KM; }
-				emit(i, (unsigned)g);
-				while (kb < k1) { // the group steps inside the stretch
-					const size_t pos = i + (size_t)(kb - k);
-					g = kb * KM / Kc; kb = ((g + 1) * Kc + KM - 1) / KM;
-					emit(pos, (unsigned)g);
-				}
-				k = k1;
-				if (j < mtr) emit(j, SIG_DELETED);
-				i = j;
-			}
-		} else { // the plain stack: min(floor(i KM / mtr), KM - 1), steps at ceil(g mtr / KM)
-			emit(0, 0);
-			for (unsigned long long g = 1; g < KM; g++) {
-				const unsigned long long pos = (g * mtr + KM - 1) / KM;
-				if (pos >= mtr) break;
-				emit((size_t)pos, (unsigned)(pos * KM / mtr));
-			}
-		}
-		if (!pc.empty()) close_piece(pc.back(), mtr);
-	}
-	for (unsigned sg = 1; sg < nstage; sg++) T[sg] = std::max(T[sg], T[sg - 1]);
-	T[nstage - 1] = mtr_local; // (traces past the last group of every column change nothing; they ride along)
-	// runs of the shard (local trace indices), cut at signature changes and stage ends
-	mp.runs.clear();
-	std::vector<unsigned> run_stage;
-	{
-		unsigned sg = 0;
-		for (size_t i = 0; i < mtr_local;) {
-			while (sg + 1 < nstage && i >= T[sg]) sg++;
-			const size_t lim = std::min(mtr_local, T[sg]);
-			size_t j = i + 1;
-			if (j < lim) { // the next trace of the shard that starts a run (bytes of chg: memchr)
-				const void *q = memchr(chg.data() + lo + j, 1, lim - j);
-				j = q ? (size_t)((const unsigned char *)q - chg.data()) - lo : lim;
-			}
-			Chunk c; c.t0 = i; c.count = (unsigned)(j - i); c.row = 0;
-			if (c.count != j - i) { j = i + 0xFFFFFFF0ull; c.count = 0xFFFFFFF0u; } // (a run longer than 2^32 traces is cut)
-			mp.runs.push_back(c);
-			run_stage.push_back(sg);
-			i = j;
-		}
-	}
-	// group of run r in column c: the piece that holds the run's first trace (the columns' pieces and the runs are both in trace order)
-	static thread_local std::vector<unsigned> rsig; // [W][runs]
-	{
-		const size_t nrr = mp.runs.size();
-		rsig.resize((size_t)W * nrr);
-		for (unsigned c = 0; c < W; c++) {
-			const std::vector<Piece> &pc = pieces[c];
-			size_t q = 0;
-			for (size_t r = 0; r < nrr; r++) {
-				const size_t t = lo + mp.runs[r].t0;
-				while (q + 1 < pc.size() && pc[q + 1].pos <= t) q++;
-				rsig[(size_t)c * nrr + r] = pc.empty() ? SIG_DELETED : pc[q].v;
-			}
-		}
-	}
-	auto SIG = [&](unsigned r, unsigned c) -> unsigned { return rsig[(size_t)c * mp.runs.size() + r]; }; // group of run r in column c
-	const unsigned nr = (unsigned)mp.runs.size();
-	mp.stage_run0.assign(nstage + 1, nr);
-	for (unsigned r = nr; r-- > 0;) mp.stage_run0[run_stage[r]] = r;
-	for (unsigned sg = nstage; sg-- > 0;) if (mp.stage_run0[sg] > mp.stage_run0[sg + 1]) mp.stage_run0[sg] = mp.stage_run0[sg + 1]; // (empty stages)
-	mp.direct = allow_direct && W <= tspws_rows_walk_wmax() && W <= 32;
-	mp.rdesc.clear(); mp.flush_rows.clear(); mp.unwritten = false;
-	if (mp.direct) {
-		std::vector<char> written((size_t)KM * W, 0);
-		mp.rdesc.resize(nr);
-		for (unsigned r = 0; r < nr; r++) { RunDesc d; memset(&d, 0, sizeof d); d.t0 = mp.runs[r].t0; d.count = mp.runs[r].count; mp.rdesc[r] = d; }
-		// column by column, from the last run back: a run that belongs to the column ends the column's group when the next run that
-		// belongs to it has another group (or there is none)
-		for (unsigned c = 0; c < W; c++) {
-			unsigned next_g = SIG_DELETED;
-			for (unsigned r = nr; r-- > 0;) {
-				const unsigned g = SIG(r, c);
-				if (g == SIG_DELETED) continue;
-				mp.rdesc[r].member |= 1u << c;
-				if (g != next_g) { mp.rdesc[r].flush |= 1u << c; written[mp.row_of(std::min(g, KM - 1), c)] = 1; }
-				next_g = g;
-			}
-		}
-		for (unsigned r = 0; r < nr; r++) { // flush destinations in ascending column order
-			mp.rdesc[r].frow = (unsigned)mp.flush_rows.size();
-			for (unsigned c = 0; c < W; c++) if ((mp.rdesc[r].flush >> c) & 1u) mp.flush_rows.push_back(mp.row_of(std::min(SIG(r, c), KM - 1), c));
-		}
-		for (char w : written) if (!w) mp.unwritten = true;
-		// two segments of similar trace counts per stage, and what the second one's first stores lack
-		mp.stage_mid.assign(nstage, 0); mp.fix_row.assign((size_t)nstage * W, ~0u);
-		for (unsigned sg = 0; sg < nstage; sg++) {
-			const unsigned q0 = mp.stage_run0[sg], q1 = mp.stage_run0[sg + 1];
-			size_t traces = 0, done = 0;
-			for (unsigned r = q0; r < q1; r++) traces += mp.runs[r].count;
-			unsigned qm = q1;
-			for (unsigned r = q0; r < q1; r++) { if (r > q0 && 2 * done >= traces) { qm = r; break; } done += mp.runs[r].count; }
-			mp.stage_mid[sg] = qm;
-			for (unsigned r = qm; r < q1; r++) {
-				unsigned fr = mp.rdesc[r].frow;
-				for (unsigned c = 0; c < W; c++)
-					if ((mp.rdesc[r].flush >> c) & 1u) { if (mp.fix_row[(size_t)sg * W + c] == ~0u) mp.fix_row[(size_t)sg * W + c] = mp.flush_rows[fr]; fr++; }
-			}
-		}
-	}
-	mp.seg_first.clear(); mp.stage_seg0.assign(nstage + 1, 0); mp.carry.clear(); mp.carry_ptr.assign(nstage + 1, 0);
-	mp.trow_ptr.assign((size_t)KM * W + 1, 0); mp.tidx.clear(); mp.tcoef.clear();
-	if (!mp.direct) { // the snapshot form: segments, carries, rows as signed sums of snapshots
-	// segments: a stage's runs in ~256 / (column blocks) pieces of similar trace counts, each walked by its own workgroups
+	// snapshot form: a stage's runs in ~256 / (column blocks) segments, each walked by its own workgroups
 	static int seg_wgs = -1; // workgroups the streaming side aims at per stage (sweeps: TSPWS_JK_SEGWG)
 	if (seg_wgs < 0) { const char *e = sweep_env("TSPWS_JK_SEGWG"); seg_wgs = e ? std::max(1, atoi(e)) : 256; }
-	const unsigned bx = (unsigned)((N + 1023) / 1024), want_seg = std::max(1u, (unsigned)seg_wgs / std::max(1u, bx));
-	mp.seg_first.clear(); mp.stage_seg0.assign(nstage + 1, 0);
-	std::vector<unsigned> seg_of(nr, 0), seg_last;      // segment (global numbering) of a run; last run of a segment
-	std::vector<unsigned> seg_stage_first(nstage + 1, 0); // first global segment of a stage
-	{
-		unsigned r = 0;
-		for (unsigned sg = 0; sg < nstage; sg++) {
-			mp.stage_seg0[sg] = (unsigned)mp.seg_first.size();
-			seg_stage_first[sg] = (unsigned)seg_last.size();
-			unsigned r1 = r;
-			size_t traces = 0;
-			while (r1 < nr && run_stage[r1] == sg) { traces += mp.runs[r1].count; r1++; }
-			const unsigned nruns = r1 - r, nseg = std::min(want_seg, nruns);
-			size_t done = 0;
-			unsigned k = 0;
-			for (unsigned q = r; q < r1; q++) {
-				// run q opens segment k when the traces before it reach k / nseg of the stage
-				if (k < nseg && (q == r || done * nseg >= (size_t)k * traces)) {
-					if (q != r) seg_last.push_back(q - 1);
-					mp.seg_first.push_back(q);
-					k++;
-				}
-				seg_of[q] = (unsigned)(seg_stage_first[sg] + k - 1);
-				done += mp.runs[q].count;
-			}
-			if (nruns) seg_last.push_back(r1 - 1);
-			mp.seg_first.push_back(r1);
-			r = r1;
-		}
-		mp.stage_seg0[nstage] = (unsigned)mp.seg_first.size();
-		seg_stage_first[nstage] = (unsigned)seg_last.size();
-	}
-	// prefix sum at the start of a stage = sum of the final snapshots of the segments of the last non-empty stage before it
-	mp.carry.clear(); mp.carry_ptr.assign(nstage + 1, 0);
-	{
-		std::vector<unsigned> cur;
-		for (unsigned sg = 0; sg < nstage; sg++) {
-			mp.carry_ptr[sg] = (unsigned)mp.carry.size();
-			mp.carry.insert(mp.carry.end(), cur.begin(), cur.end());
-			if (seg_stage_first[sg + 1] > seg_stage_first[sg]) {
-				cur.clear();
-				for (unsigned q = seg_stage_first[sg]; q < seg_stage_first[sg + 1]; q++) cur.push_back(seg_last[q]);
-			}
-		}
-		mp.carry_ptr[nstage] = (unsigned)mp.carry.size();
-	}
-	// G(k) = sum of all traces before run k, as a signed sum of snapshots: snap[k - 1] + the final snapshots of the earlier segments
-	// of the same stage (segment 0 of a stage starts from the carried prefix: its snapshots are global)
-	auto add_G = [&](std::vector<std::pair<unsigned, int>> &terms, unsigned k, int sign) {
-		if (!k) return;
-		const unsigned r = k - 1, sg = run_stage[r];
-		terms.emplace_back(r, sign);
-		for (unsigned q = seg_stage_first[sg]; q < seg_of[r]; q++) terms.emplace_back(seg_last[q], sign);
-	};
-	// rows: for every column and group the maximal stretches [a, b) of consecutive runs that belong to it: sum of G(b) - G(a)
-	const unsigned nrow = KM * W;
-	std::vector<std::vector<std::pair<unsigned, int>>> lists(nrow);
-	for (unsigned c = 0; c < W; c++) {
-		unsigned a = 0, cur = SIG_DELETED;
-		for (unsigned r = 0; r <= nr; r++) {
-			const unsigned g = r < nr ? SIG(r, c) : SIG_DELETED;
-			if (g == cur) continue;
-			if (cur != SIG_DELETED) { auto &L = lists[mp.row_of(std::min(cur, KM - 1), c)]; add_G(L, r, +1); add_G(L, a, -1); }
-			cur = g; a = r;
-		}
-	}
-	mp.trow_ptr.assign((size_t)nrow + 1, 0); mp.tidx.clear(); mp.tcoef.clear();
-	for (unsigned r = 0; r < nrow; r++) {
-		mp.trow_ptr[r] = (unsigned)mp.tidx.size();
-		auto &L = lists[r];
-		std::sort(L.begin(), L.end());
-		for (size_t i = 0; i < L.size();) { // merge equal snapshots, drop what cancels
-			size_t j = i; int cf = 0;
-			while (j < L.size() && L[j].first == L[i].first) cf += L[j++].second;
-			if (cf) { mp.tidx.push_back(L[i].first); mp.tcoef.push_back((float)cf); }
-			i = j;
-		}
-	}
-	mp.trow_ptr[nrow] = (unsigned)mp.tidx.size();
-	} // (snapshot form)
-	mp.rowmap.assign((size_t)W * KM, 0);
-	for (unsigned c = 0; c < W; c++) for (unsigned g = 0; g < KM; g++) mp.rowmap[(size_t)c * KM + g] = mp.row_of(g, c);
-	mp.Mv.assign(W, 0.0);
-	for (unsigned c = 0; c < C; c++) mp.Mv[c] = (double)mp.Kc[c];
-	if (with_main) mp.Mv[C] = (double)(unsigned)mtr;
-	// one block for the device: runs (16-byte records) | trace counts | run descriptors | term pointers | term snapshots | term
-	// coefficients | row map | segments | carries | flush rows | fix rows -- ONE host-to-device copy per new selection
-	{
-		const size_t n_runs = mp.direct ? 0 : mp.runs.size(), n_tp = mp.trow_ptr.size(), n_t = mp.tidx.size(), n_map = mp.rowmap.size(), n_seg = mp.seg_first.size(),
-		             n_car = mp.carry.size(), n_rd = mp.rdesc.size(), n_fr = mp.flush_rows.size(), n_fx = mp.fix_row.size();
-		mp.o_mv = n_runs * sizeof(Chunk); mp.o_rd = mp.o_mv + W * sizeof(double); mp.o_tp = mp.o_rd + n_rd * sizeof(RunDesc); mp.o_ti = mp.o_tp + n_tp * 4;
-		mp.o_tc = mp.o_ti + n_t * 4; mp.o_map = mp.o_tc + n_t * 4; mp.o_seg = mp.o_map + n_map * 4; mp.o_car = mp.o_seg + n_seg * 4; mp.o_fr = mp.o_car + n_car * 4;
-		mp.o_fx = mp.o_fr + n_fr * 4;
-		mp.blob.assign(mp.o_fx + std::max<size_t>(n_fx, 1) * 4, 0);
-		char *b = mp.blob.data();
-		if (n_runs) memcpy(b, mp.runs.data(), n_runs * sizeof(Chunk));
-		memcpy(b + mp.o_mv, mp.Mv.data(), W * sizeof(double));
-		if (n_rd) memcpy(b + mp.o_rd, mp.rdesc.data(), n_rd * sizeof(RunDesc));
-		memcpy(b + mp.o_tp, mp.trow_ptr.data(), n_tp * 4);
-		if (n_t) { memcpy(b + mp.o_ti, mp.tidx.data(), n_t * 4); memcpy(b + mp.o_tc, mp.tcoef.data(), n_t * 4); }
-		memcpy(b + mp.o_map, mp.rowmap.data(), n_map * 4);
-		if (n_seg) memcpy(b + mp.o_seg, mp.seg_first.data(), n_seg * 4);
-		if (n_car) memcpy(b + mp.o_car, mp.carry.data(), n_car * 4);
-		if (n_fr) memcpy(b + mp.o_fr, mp.flush_rows.data(), n_fr * 4);
-		if (n_fx) memcpy(b + mp.o_fx, mp.fix_row.data(), n_fx * 4);
-	}
-	mp.mtr = mtr; mp.N = N; mp.C = C; mp.with_main = with_main; mp.nstage = nstage; mp.allow_direct = allow_direct; mp.first = first; mp.mtr_local = mtr_local;
+	const bool direct = allow_direct && C + (with_main ? 1u : 0u) <= tspws_rows_walk_wmax();
+	masked_build(mp, work, mtr, h_sel, C, KM, with_main, gps, direct, masked_want_seg(N, (unsigned)seg_wgs), first, mtr_local);
+	mp.N = N; mp.allow_direct = allow_direct;
 	mp.sel.assign(h_sel, h_sel + (size_t)C * mtr);
 	mp.gen = next_masked_gen();
 	mp.valid = true;

@@ -20,7 +20,9 @@
 //   replica_bands.hip  percentile bands over the replica rows those calls leave (its own table slot, SCR_RBTAB)
 //   trace_scores.hip   similarity / misfit of every trace against reference rows, the selective stack (its own slots: SCR_TSTAB the group
 //                 table, SCR_TSP the partial sums, SCR_TSOUT the selective stack's score planes)
-//                 (batch_kernels.h: the kernels those units share; batch_host.h: their host scaffold -- upload lifetime, table layouts, rounds)
+//                 (batch_kernels.h: the kernels those units share; batch_host.h: their host scaffold -- upload lifetime, rounds)
+//   column_runs.h   host only: the group signature of the two-stage replicas' columns, runs, column bits, the layout of a table block
+//   masked_tables.h host only: the run tables of the masked replicas of one ensemble (resample.hip), in steps
 //   comm.hip      trace shards on several devices of one process: RCCL all-reduce, sharded tspws_main driver
 //
 // Layout in HBM
@@ -44,6 +46,7 @@
 #include <vector>
 
 #include "tspws_hip.h"
+#include "column_runs.h" // Chunk, RunDesc, TableLayout: host-only definitions that the kernels' tables share with the CPU checks
 
 #ifndef TSPWS_PI
 #define TSPWS_PI 3.14159265358979328
@@ -96,20 +99,6 @@ struct ScaleDesc {
 	unsigned fuse_ok;           // 1: k_fwd_lds<FUSE> keeps this scale's linear / phase stacks in registers (no partials)
 	unsigned r16;               // 1: the direct kernel gives a thread 16 outputs of this scale (ngw counts 16-output groups)
 	unsigned long long part_off; // offset of this scale's [nsplit][Ns] partial block
-};
-
-struct Chunk { // one streaming work item of the partial-stack kernel
-	unsigned long long t0; // first local trace
-	unsigned count;        // traces
-	unsigned row;          // destination row (group / class)
-};
-
-struct RunDesc { // one run of consecutive traces with one signature, for k_rows_walk (stream.hip)
-	unsigned long long t0;   // first trace
-	unsigned count;          // traces
-	unsigned member, flush;  // bit c: the run belongs to column c / column c's group ends with this run
-	unsigned frow;           // first entry of the run's flush destinations in flush_rows (ascending column order)
-	unsigned pad[2];
 };
 
 // A contiguous run of scales [s0, s1) a finish-stage launch is restricted to (scale-sharded finish); s1 == 0: all scales.
