@@ -657,6 +657,56 @@ int  tspws_hip_selective_stack_batch(tspws_hip_plan *plan, const t_tsPWS *p, con
                                      int against, int rule, double a, unsigned iters, size_t n0, size_t n1, float *d_ls, float *d_tsPWS,
                                      char *h_sel, unsigned *h_kept, unsigned *iters_done, void *stream);
 
+/* ---- dv/v by stretching of stack rows ---- */
+/* The stretching estimate of dv/v for the rows the batched calls leave: per (row, window) the correlation coefficient of the row with its
+ * ensemble's reference row evaluated at lag t (1 + eps), on a grid of E stretch factors, and the maximum with a three-point fit.
+ * d_rows is [B][M][ld] floats on the plan's device (d_ls_out / d_ts_out of the batched calls: ld >= max = N), h_mtr NULL or [B][M] host
+ * counts: row (b, m) takes part iff h_mtr == NULL or h_mtr[b][m] > 0 (tspws_hip_replica_bands' rule).  d_ref is [B][ldr] floats, one
+ * reference row per ensemble, ldr >= max (band rows [B][R][max]: B R ensembles of M = 1).  z is the zero-lag position in samples; it may be
+ * fractional or outside [0, N).  h_eps[E] increases strictly, |eps| <= 0.5, 1 <= E <= 4096.  h_win holds W pairs [n0_w, n1_w),
+ * n0 < n1 <= N, 1 <= W <= 4; windows may overlap.
+ * Definition, in FP64 with every operation rounded on its own (no contraction): for sample n and stretch e
+ *   u = (double)n + ((double)n - z) * eps_e, i = floor(u), f = u - i,
+ *   w-1 = ((-0.5 f + 1) f - 0.5) f,  w0 = (1.5 f - 2.5) f f + 1,  w1 = ((-1.5 f + 2) f + 0.5) f,  w2 = (0.5 f - 0.5) f f
+ *   S_e[n] = ((w-1 ref[i-1] + w0 ref[i]) + w1 ref[i+1]) + w2 ref[i+2]     (cubic convolution, Keys a = -1/2; samples outside [0, N) are zero)
+ * so eps = 0 gives S[n] = ref[n] exactly; and per (b, m, w, e), over n0_w <= n < n1_w with c the row,
+ *   dot = sum (double)c[n] S_e[n],   cc = dot / sqrt(sum c^2) / sqrt(sum S_e^2)      (the reference's similarity order)
+ * A dead row or a dead stretched reference gives the reference's NaN (0 / 0).  With this definition cur(t) = ref(t (1 + eps)), so the eps
+ * of the maximum is dv/v.
+ * d_cc is NULL or [B][M][W][E] doubles; d_fit is [B][M][W][4] doubles: eps_hat, cc_hat, (double)e*, edge.  e* = the first index of the largest
+ * non-NaN cc.  With c- = cc[e* - 1], c0 = cc[e*], c+ = cc[e* + 1]: when 0 < e* < E - 1 and den = c- - 2 c0 + c+ != 0,
+ *   d = 0.5 (c- - c+) / den,  eps_hat = eps[e*] + d * (d >= 0 ? eps[e* + 1] - eps[e*] : eps[e*] - eps[e* - 1]),
+ *   cc_hat = c0 - 0.25 (c- - c+) d,  edge = 0;
+ * otherwise eps_hat = eps[e*], cc_hat = c0, edge = 1.  Without a non-NaN cc, or for a row that does not take part, d_fit is NaN, NaN, -1, 1
+ * and the row's d_cc entries are NaN.
+ * Nothing is atomic and every sum has a fixed order: a repeated call is bit-identical, and the values of (b, m, w, e) depend only on that
+ * row, its reference, z, eps_e and window w -- not on B, M, the other grid entries, the other windows, the rounds or a tile's padding.
+ * Three kernels: the stretched references S of a round in FP64 (built once per ensemble, shared by its M rows) with the per-segment sums
+ * of S^2; the contraction rows . S on v_mfma_f64_16x16x4_f64, one wave per (up to 32 rows, up to 64 stretches, segment of 512 window
+ * samples), which also leaves sum c^2; a final kernel that adds the segments in segment order, forms cc and the fit.  In rounds of (whole
+ * ensembles x chunks of the grid in multiples of 16) so that S and the partial sums stay within TSPWS_PART_MB (one ensemble x 16 stretches
+ * alone may exceed it); one small table upload per round into scratch slots of the unit's own.
+ * NULL plan / d_rows / d_ref / h_eps / h_win / d_fit, ld < max, ldr < max, E or W outside its range, a grid that does not increase strictly,
+ * a NaN grid entry or one with |eps| > 0.5, a NaN or infinite z, and a bad window (n0 >= n1, n1 > max) return TSPWS_E_ARG
+ * ("stretch_rows: ...") before any device work, outputs untouched; the checks that need no plan come first.  So do more than 2^32 - 16 rows.
+ * B == 0 or M == 0 returns 0 and does nothing.  Columns max .. ld-1 / ldr-1 are never read, nothing outside the two outputs is written.
+ * The call waits for `stream`: on return the outputs are complete. */
+int  tspws_hip_stretch_rows(tspws_hip_plan *plan, const float *d_rows, size_t ld, unsigned B, unsigned M, const unsigned *h_mtr,
+                            const float *d_ref, size_t ldr, double z, const double *h_eps, unsigned E, const size_t *h_win, unsigned W,
+                            double *d_cc, double *d_fit, void *stream);
+/* How the plan's last tspws_hip_stretch_rows call with B, M > 0 went (all zero before the first one). */
+typedef struct {
+	unsigned rounds;   /* rounds of whole ensembles                                  */
+	unsigned segments; /* column segments of the window set (all windows together)   */
+	unsigned rows;     /* rows that took part                                        */
+	unsigned left_out; /* rows left out by h_mtr                                     */
+	unsigned chunks;   /* chunks of the stretch grid per round (the largest count)   */
+} tspws_hip_stretch_stats;
+int  tspws_hip_stretch_rows_stats(const tspws_hip_plan *plan, tspws_hip_stretch_stats *stats);
+/* Host: the symmetric stretch grid eps[e] = ((double)e - h) * (eps_max / h), h = (E - 1) / 2, for an odd E >= 3: the middle entry is
+ * exactly 0.  Returns 0; 1 for NULL eps; 2 for an even E, E < 3 or an eps_max outside (0, 0.5] (nothing written). */
+int  tspws_stretch_grid(double *eps, double eps_max, unsigned E);
+
 /* ---- convergence curves ------------------------------------------------------------------------ */
 /* Similarity / misfit of the stack of the first i+1 traces against a reference, for i = 0..mtr-1
  * (ts_pws1f_lib.c:247-314, similarity :433-449, misfit :452-462).  d_ref_ts / d_ref_ls are [max] floats on the

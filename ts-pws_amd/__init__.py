@@ -161,6 +161,9 @@ SYMBOLS = {
     "tspws_hip_trace_scores": (_i, [_vp, _vp, _sz, _vp, _u, _vp, _sz, _u, _sz, _sz, _vp, _vp, _vp]),
     "tspws_hip_trace_scores_stats": (_i, [_vp, _vp]),
     "tspws_selection_from_scores": (_i, [_vp, _vp, _vp, _vp, _u, _i, _d]),
+    "tspws_hip_stretch_rows": (_i, [_vp, _vp, _sz, _u, _u, _vp, _vp, _sz, _d, _vp, _u, _vp, _u, _vp, _vp, _vp]),
+    "tspws_hip_stretch_rows_stats": (_i, [_vp, _vp]),
+    "tspws_stretch_grid": (_i, [_vp, _d, _u]),
     "tspws_hip_selective_stack_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _i, _i, _d, _u, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -951,6 +954,72 @@ class Plan:
                                                        kept.ctypes.data, C.byref(done), self._stream()), "selective_stack_batch")
         return ls, ts, sel, kept, done.value
 
+    def stretch_rows(self, rows, ref, z, eps, windows, mtr=None, cc=False, out=None):
+        """dv/v by stretching (tspws_hip_stretch_rows): the correlation coefficient of every row of `rows` (float32 cuda [B][M][N], contiguous
+        or a [:, :, :N] view of a [B][M][ld] base: ls_out / ts_out of the batched calls) with its ensemble's reference row `ref` (float32 cuda
+        [B][N], contiguous or a [:, :N] view) evaluated at lag t (1 + eps), for the strictly increasing stretch factors `eps` (|eps| <= 0.5, at
+        most 4096; see stretch_grid) over the 1 to 4 `windows` (n0, n1) of samples n0 <= n < n1; `z` = the zero-lag position in samples.
+        `mtr` = None or the rows' uint32 [B][M] counts: row (b, m) takes part iff mtr is None or mtr[b][m] > 0.  Returns the fit plane, float64
+        cuda [B][M][W][4] = eps_hat (dv/v), cc_hat, e*, edge; with cc=True the pair (cc [B][M][W][E], fit).  `out` = None, or the tensor(s)
+        to write: a contiguous float64 cuda tensor of at least B M W 4 values (cc=True: the pair (cc, fit), cc of at least B M W E values),
+        returned as given.  New outputs hold NaN before the call.  Synchronises."""
+        import numpy as np
+        import torch
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[2] != self.N:
+            raise TspwsError(f"rows must be a float32 [B][M][{self.N}] tensor, got {getattr(rows, 'dtype', type(rows))} {tuple(getattr(rows, 'shape', ()))}")
+        if not rows.is_cuda or (rows.device.index or 0) != self.device:
+            raise TspwsError(f"rows live on {rows.device}, the plan on cuda:{self.device}")
+        B, Mn = rows.shape[0], rows.shape[1]
+        ld = rows.stride(1) if Mn > 1 else (rows.stride(0) if B > 1 else self.N)
+        if B and Mn:
+            if rows.stride(2) != 1:
+                raise TspwsError("rows must be contiguous along the samples (stride(2) == 1)")
+            if ld < self.N:
+                raise TspwsError("overlapping rows (row stride < N)")
+            if B > 1 and rows.stride(0) != Mn * ld:
+                raise TspwsError("rows must be a [B][M][N] view of one [B][M][ld] base (stride(0) == M * stride(1))")
+        if not isinstance(ref, torch.Tensor) or ref.dtype != torch.float32 or tuple(ref.shape) != (B, self.N):
+            raise TspwsError(f"ref must be a float32 [{B}][{self.N}] tensor, got {getattr(ref, 'dtype', type(ref))} {tuple(getattr(ref, 'shape', ()))}")
+        if not ref.is_cuda or (ref.device.index or 0) != self.device:
+            raise TspwsError(f"ref lives on {ref.device}, the plan on cuda:{self.device}")
+        ldr = ref.stride(0) if B > 1 else self.N
+        if B and (ref.stride(1) != 1 or ldr < self.N):
+            raise TspwsError("ref must be contiguous along the samples, its rows not overlapping")
+        try:
+            ea = np.ascontiguousarray(np.asarray(eps, dtype=np.float64))
+            wa = np.ascontiguousarray(np.asarray(windows, dtype=np.int64))
+        except (TypeError, ValueError):
+            raise TspwsError("eps must be a sequence of floats, windows a sequence of (n0, n1) pairs") from None
+        if ea.ndim != 1 or wa.ndim != 2 or wa.shape[1] != 2 or (wa < 0).any():
+            raise TspwsError("eps must be a sequence of floats, windows a sequence of (n0, n1) pairs of non-negative integers")
+        wa = np.ascontiguousarray(wa, dtype=np.uint64)  # size_t
+        E, W = ea.size, wa.shape[0]
+        if mtr is not None:
+            if not isinstance(mtr, np.ndarray) or mtr.dtype != np.uint32 or mtr.shape != (B, Mn):
+                raise TspwsError(f"mtr must be None or a uint32 numpy array [{B}][{Mn}]")
+            mtr = np.ascontiguousarray(mtr)
+        o_cc, o_fit = (out if cc else (None, out)) if out is not None else (None, None)
+        if out is None:
+            o_fit = torch.full((B, Mn, W, 4), float("nan"), dtype=torch.float64, device=rows.device)
+            o_cc = torch.full((B, Mn, W, E), float("nan"), dtype=torch.float64, device=rows.device) if cc else None
+        for t, n, name in ((o_fit, 4, "fit"), (o_cc, E, "cc")):
+            if t is None and name == "cc" and not cc:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.numel() < B * Mn * W * n or not t.is_contiguous() or not t.is_cuda or \
+                    (t.device.index or 0) != self.device:
+                raise TspwsError(f"out: {name} must be a contiguous float64 tensor of >= {B * Mn * W * n} values on cuda:{self.device}")
+        if B and Mn:  # (an empty tensor has no address)
+            check(self.lib.tspws_hip_stretch_rows(self.h, rows.data_ptr(), ld, B, Mn, mtr.ctypes.data if mtr is not None else None, ref.data_ptr(), ldr,
+                                                  float(z), ea.ctypes.data, E, wa.ctypes.data, W, o_cc.data_ptr() if cc else None, o_fit.data_ptr(),
+                                                  self._stream()), "stretch_rows")
+        return (o_cc, o_fit) if cc else o_fit
+
+    def stretch_rows_stats(self):
+        """How the last stretch_rows call with B, M > 0 went (tspws_hip_stretch_rows_stats): dict(rounds, segments, rows, left_out, chunks)."""
+        st = (C.c_uint * 5)()
+        check(self.lib.tspws_hip_stretch_rows_stats(self.h, C.byref(st)), "stretch_rows_stats")
+        return dict(zip(("rounds", "segments", "rows", "left_out", "chunks"), list(st)))
+
     def _refs(self, t, name, rows):
         """Data pointer of a reference array: contiguous float32 [rows][N] (or [N] for one row) on the plan's device."""
         import torch
@@ -1316,6 +1385,17 @@ def selection_from_scores(score, first, rule, a):
     if rc:
         raise TspwsError(f"tspws_selection_from_scores refused its arguments (code {rc})")
     return sel, kept
+
+
+def stretch_grid(eps_max, E):
+    """The symmetric stretch grid of tspws_stretch_grid: float64 [E], eps[e] = (e - h) * (eps_max / h), h = (E - 1) / 2; E odd and >= 3,
+    0 < eps_max <= 0.5.  The middle entry is exactly 0."""
+    import numpy as np
+    eps = np.zeros(max(int(E), 0), np.float64)
+    rc = load().tspws_stretch_grid(eps.ctypes.data, float(eps_max), int(E)) if 0 <= int(E) < 2 ** 32 else 2
+    if rc:
+        raise TspwsError(f"tspws_stretch_grid refused its arguments (code {rc}): E odd and >= 3, 0 < eps_max <= 0.5")
+    return eps
 
 
 def band_table(bands):
