@@ -97,3 +97,47 @@ def test_selection_helper_matches_the_oracle(lib, n, d):
         tspws.jackknife_selection_batch(bad, first, n, d)
     with pytest.raises(tspws.TspwsError):
         tspws.jackknife_selection_batch(times, [0, 5, 3], n, d)
+
+
+# ---- the module-level helpers' check of `first` -------------------------------------------------------------------------------------------
+# one good `first` (offset start, an empty ensemble) and one plane of scores; the expected arrays were recorded from the binding as it was
+# before its helpers shared one check of `first` (abi.srand(5) before the two drawing helpers)
+FIRST = [3, 3, 7]
+TIMES = 1_000_000_000 + 86400 * 40 * np.arange(7)
+SCORE = np.array([0.9, float("nan"), 0.2, 0.85])
+HELPERS = {
+    "jackknife_selection_batch": lambda f: tspws.jackknife_selection_batch(TIMES, f, 4, 1),
+    "subsampling_selection_batch": lambda f: tspws.subsampling_selection_batch(f, 3, 0.5),
+    "bootstrap_counts_batch": lambda f: tspws.bootstrap_counts_batch(f, 3),
+    "selection_from_scores": lambda f: tspws.selection_from_scores(SCORE, f, "threshold", 0.5),
+    "weights_from_scores": lambda f: tspws.weights_from_scores(SCORE, f, "power", 2.0),
+}
+BAD_FIRST = {"2-D": [[0, 1], [2, 3]], "float": [0.0, 1.0], "negative": [-1, 2], "decreasing": [0, 5, 4], "empty": []}
+
+
+@pytest.mark.parametrize("bad", sorted(BAD_FIRST))
+@pytest.mark.parametrize("helper", sorted(HELPERS))
+def test_helpers_refuse_a_bad_first(lib, helper, bad):
+    with pytest.raises(tspws.TspwsError):
+        HELPERS[helper](BAD_FIRST[bad])
+
+
+@pytest.mark.parametrize("as_array", [list, lambda f: np.array(f, np.int32), lambda f: np.array(f, np.uint64)])
+def test_helpers_on_a_good_first(lib, as_array):
+    f = as_array(FIRST)
+    jk = HELPERS["jackknife_selection_batch"](f)
+    assert jk.dtype == np.int8 and jk.tolist() == [[0, 0, 0, 1], [1, 1, 1, 0], [1, 1, 1, 1], [1, 1, 1, 1]]
+    abi.srand(5)
+    sub = HELPERS["subsampling_selection_batch"](f)
+    assert sub.dtype == np.int8 and sub.tolist() == [[1, 0, 1, 0], [0, 1, 0, 1], [0, 0, 1, 1]]
+    abi.srand(5)
+    cnt = HELPERS["bootstrap_counts_batch"](f)
+    assert cnt.dtype == np.uint8 and cnt.tolist() == [[2, 1, 0, 1], [2, 2, 0, 0], [1, 2, 0, 1]]
+    sel, kept = HELPERS["selection_from_scores"](f)
+    assert (sel.dtype, sel.tolist(), kept.dtype, kept.tolist()) == (np.int8, [1, 0, 0, 1], np.uint32, [0, 2])
+    sel, kept = tspws.selection_from_scores(SCORE, f, "mad", 1.0)
+    assert (sel.tolist(), kept.tolist()) == ([1, 0, 0, 1], [0, 2])
+    w = HELPERS["weights_from_scores"](f)
+    assert w.dtype == np.float64 and [x.hex() for x in w] == ["0x1.9eb851eb851ecp-1", "0x0.0p+0", "0x1.47ae147ae147cp-5", "0x1.71eb851eb851ep-1"]
+    w = tspws.weights_from_scores(SCORE, f, "inverse")
+    assert [x.hex() for x in w] == ["0x1.c71c71c71c71dp-3", "0x0.0p+0", "0x1.0000000000000p+0", "0x1.e1e1e1e1e1e1ep-3"]

@@ -12,6 +12,17 @@ is present the calls raise.
 
 Import with ``importlib.import_module("ts-pws_amd")`` (the directory name is
 not a Python identifier).
+
+Every argument check exists once; a new batched call takes them from here
+rather than from a sibling method.  Module level: ``_offsets`` (``first`` ->
+uint64 offsets, B, T), ``_host_array`` (numpy array of dtype and shape:
+``mtr_out``, ``mtr``), ``_score_plane`` (``score`` -> float64 [T]).  On
+``Plan``: ``_traces`` (the trace rows), ``_need`` (contiguous tensor of a dtype
+on the plan's device, of a shape or of at least so many elements; ``_out`` and
+``_refs`` are its pointer-returning forms), ``_rows_out`` (``ls_out`` /
+``ts_out`` / ``mtr_out``, given or new), ``_sel`` (selections and masks),
+``_coef_sets`` (``Y``), ``_strided_rows`` ([B][M][N] views of a wider base),
+``_window`` and ``_stats`` (the ``*_stats()`` dicts).
 """
 import ctypes as C
 import os
@@ -216,6 +227,42 @@ def check(rc, what=""):
         raise TspwsError(f"{what} failed with code {rc}: {load().tspws_hip_last_error().decode()}")
 
 
+def _offsets(first, limit=None, rows="trace rows"):
+    """(first as contiguous uint64, B, T) of B + 1 ensemble offsets, T = first[B] - first[0]; `limit` = how many `rows` they index into
+    (None: no upper limit).  Converted offsets pass again unchanged."""
+    import numpy as np
+    f = np.asarray(first)
+    if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
+        raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
+    if (f < 0).any() or (np.diff(f) < 0).any() or (limit is not None and int(f[-1]) > limit):
+        raise TspwsError("first must be non-decreasing offsets" + (f" into the {limit} {rows}" if limit is not None else " >= 0"))
+    f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
+    return f, f.size - 1, int(f[-1] - f[0])
+
+
+def _host_array(a, name, dtype, shape, optional=False):
+    """`a` as a contiguous numpy array after checking its dtype and shape.  optional=True is the `mtr` of replica_bands / stretch_rows:
+    None passes, and so does an array with strides (it is copied)."""
+    import numpy as np
+    if a is None and optional:
+        return None
+    if not isinstance(a, np.ndarray) or a.dtype != dtype or a.shape != shape or not (optional or a.flags.c_contiguous):
+        dims = f"of {shape[0]} entries" if len(shape) == 1 else "".join(f"[{n}]" for n in shape)
+        raise TspwsError(f"{name} must be {'None or a' if optional else 'a contiguous'} {np.dtype(dtype).name} numpy array {dims}")
+    return a if a.flags.c_contiguous else np.ascontiguousarray(a)
+
+
+def _score_plane(score, T):
+    """One plane of T scores (numpy, a sequence or a tensor anywhere) as contiguous float64 [T]."""
+    import numpy as np
+    if hasattr(score, "detach"):
+        score = score.detach().cpu().numpy()
+    sc = np.ascontiguousarray(score, dtype=np.float64)
+    if sc.shape != (T,):
+        raise TspwsError(f"score must be one plane of {T} scores, got {sc.shape}")
+    return sc
+
+
 def resolve(params, nsamp, dt=1.0):
     """Resolved copy of a t_tsPWS (tspws_resolve_params; reference ts_pws1f_lib.c:91-124)."""
     p = t_tsPWS.from_buffer_copy(params)
@@ -294,11 +341,80 @@ class Plan:
             raise TspwsError("overlapping trace rows (stride(0) < N)")
         return mtr, ld
 
-    def _out(self, t, name):
+    def _need(self, t, name, dt, size, what="{} tensor", exact=False):
+        """Raise unless `t` is a contiguous tensor of dtype `dt` ("float32" / "float64") on the plan's device, of exactly the shape `size` (a
+        tuple) or of at least (exact=True: exactly) `size` elements (an int).  `what` words the size in the message; {} stands for `size`."""
         import torch
-        if t.dtype != torch.float32 or t.numel() < self.N or not t.is_contiguous() or not t.is_cuda or (t.device.index or 0) != self.device:
-            raise TspwsError(f"{name} must be a contiguous float32 tensor of >= {self.N} samples on cuda:{self.device}")
+        if not isinstance(t, torch.Tensor) or t.dtype != getattr(torch, dt) or not t.is_contiguous() or not t.is_cuda or (t.device.index or 0) != self.device or \
+                (tuple(t.shape) != size if isinstance(size, tuple) else t.numel() < size or (exact and t.numel() != size)):
+            dims = "".join(f"[{n}]" for n in size) if isinstance(size, tuple) else size
+            raise TspwsError(f"{name} must be a contiguous {dt} {what.format(dims)} on cuda:{self.device}")
+
+    def _out(self, t, name):
+        self._need(t, name, "float32", self.N, "tensor of >= {} samples")
         return t.data_ptr()
+
+    def _refs(self, t, name, rows):
+        """Data pointer of a reference array: contiguous float32 [rows][N] (or [N] for one row) on the plan's device."""
+        one = rows == 1 and getattr(t, "ndim", 2) == 1
+        self._need(t, name, "float32", (self.N,) if one else (rows, self.N), f"[{rows}][{self.N}] tensor")
+        return t.data_ptr()
+
+    def _rows_out(self, lead, device, ls_out, ts_out, mtr_out=None, counts=True, new="empty", what="{} tensor"):
+        """ls_out / ts_out (float32 [*lead][N] on the plan's device) and mtr_out (uint32 numpy [*lead]; None with counts=False), each as
+        given or new, and checked.  `new` = the torch constructor of a missing tensor ("empty" / "zeros"), or None: nothing may be missing."""
+        import numpy as np
+        import torch
+        if new is not None:
+            ls_out = getattr(torch, new)((*lead, self.N), dtype=torch.float32, device=device) if ls_out is None else ls_out
+            ts_out = getattr(torch, new)((*lead, self.N), dtype=torch.float32, device=device) if ts_out is None else ts_out
+            mtr_out = np.zeros(lead, np.uint32) if mtr_out is None and counts else mtr_out
+        if counts:
+            _host_array(mtr_out, "mtr_out", np.uint32, lead)
+        self._need(ls_out, "ls_out", "float32", (*lead, self.N), what)
+        self._need(ts_out, "ts_out", "float32", (*lead, self.N), what)
+        return ls_out, ts_out, mtr_out
+
+    def _coef_sets(self, Y, what):
+        """(Y on the plan's device, whether it came as numpy) of the coefficient sets Y[`what`][ncoef]: a complex128 numpy array or a
+        contiguous complex128 tensor on the plan's device."""
+        import numpy as np
+        import torch
+        if not isinstance(Y, (np.ndarray, torch.Tensor)):
+            raise TspwsError("Y must be a complex128 numpy array or device tensor")
+        host = isinstance(Y, np.ndarray)
+        if Y.dtype != (np.complex128 if host else torch.complex128) or Y.ndim != 2 or Y.shape[1] != self.ncoef or not Y.shape[0]:
+            raise TspwsError(f"Y must be complex128 [{what} >= 1][{self.ncoef}], got {Y.dtype} {tuple(Y.shape)}")
+        if host:
+            return torch.as_tensor(np.ascontiguousarray(Y), device=f"cuda:{self.device}"), True
+        if not Y.is_cuda or (Y.device.index or 0) != self.device or not Y.is_contiguous():
+            raise TspwsError(f"Y must be a contiguous tensor on cuda:{self.device}, got {Y.device}")
+        return Y, False
+
+    def _strided_rows(self, t, name="rows", kind="", mid="M"):
+        """(B, M, ld) of float32 [B][M][N] rows on the plan's device, contiguous or a [:, :, :N] view of one [B][M][ld] base.  The words of
+        the messages: `name` of the argument, `kind` of rows ("replica ", "reference "), `mid` = the letter of the middle dimension."""
+        import torch
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] != self.N:
+            raise TspwsError(f"{name} must be a float32 [B][{mid}][{self.N}] tensor, got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if not t.is_cuda or (t.device.index or 0) != self.device:
+            raise TspwsError(f"{name} live on {t.device}, the plan on cuda:{self.device}")
+        B, Mn = t.shape[0], t.shape[1]
+        ld = t.stride(1) if Mn > 1 else (t.stride(0) if B > 1 else self.N)
+        if B and Mn:
+            if t.stride(2) != 1:
+                raise TspwsError(f"{name} must be contiguous along the samples (stride(2) == 1)")
+            if ld < self.N:
+                raise TspwsError(f"overlapping {kind}rows (row stride < N)")
+            if B > 1 and t.stride(0) != Mn * ld:
+                raise TspwsError(f"{name} must be a [B][{mid}][N] view of one [B][{mid}][ld] base (stride(0) == {mid} * stride(1))")
+        return B, Mn, ld
+
+    def _stats(self, what, names):
+        """dict(names -> counts) of tspws_hip_<what> (len(names) unsigned counters)."""
+        st = (C.c_uint * len(names))()
+        check(getattr(self.lib, "tspws_hip_" + what)(self.h, C.byref(st)), what)
+        return dict(zip(names, list(st)))
 
     def stacks(self, traces):
         """The two FP64 planes of the rows of `traces` -- linear stack ST = sum Y_t and phase stack PS = sum Y_t / |Y_t| -- as complex128
@@ -329,52 +445,28 @@ class Plan:
         """Real part of the inverse frame transform of the coefficient sets Y[nrec][ncoef] in ONE tspws_hip_inverse call: a complex128 numpy
         array (returns float64 numpy [nrec][N]) or a contiguous complex128 tensor on the plan's device (returns a float64 tensor there).
         The output holds NaN before the call (an unwritten sample shows); synchronises."""
-        import numpy as np
         import torch
-        if isinstance(Y, np.ndarray):
-            if Y.dtype != np.complex128 or Y.ndim != 2 or Y.shape[1] != self.ncoef or not Y.shape[0]:
-                raise TspwsError(f"Y must be complex128 [nrec >= 1][{self.ncoef}], got {Y.dtype} {Y.shape}")
-            Yd = torch.as_tensor(np.ascontiguousarray(Y), device=f"cuda:{self.device}")
-        elif isinstance(Y, torch.Tensor):
-            if Y.dtype != torch.complex128 or Y.dim() != 2 or Y.shape[1] != self.ncoef or not Y.shape[0]:
-                raise TspwsError(f"Y must be complex128 [nrec >= 1][{self.ncoef}], got {Y.dtype} {tuple(Y.shape)}")
-            if not Y.is_cuda or (Y.device.index or 0) != self.device or not Y.is_contiguous():
-                raise TspwsError(f"Y must be a contiguous tensor on cuda:{self.device}, got {Y.device}")
-            Yd = Y
-        else:
-            raise TspwsError("Y must be a complex128 numpy array or device tensor")
+        Yd, host = self._coef_sets(Y, "nrec")
         x = torch.full((Yd.shape[0], self.N), float("nan"), dtype=torch.float64, device=Yd.device)
         check(self.lib.tspws_hip_inverse(self.h, Yd.data_ptr(), Yd.shape[0], x.data_ptr(), self._stream()), "inverse")
         torch.cuda.synchronize(Yd.device)
-        return x.cpu().numpy() if isinstance(Y, np.ndarray) else x
+        return x.cpu().numpy() if host else x
 
     def inverse_bands(self, Y, bands, quadrature=False):
         """Band rows of the coefficient sets Y[nset][ncoef] in ONE tspws_hip_inverse_bands call: `bands` = R half-open scale ranges
         (s_begin, s_end), which may overlap, cut an octave between voices or be empty.  Returns X[nset][R][N] (float64) -- row r = the sum of
         the reconstruction's scale rows s_begin <= s < s_end -- or, with quadrature=True, (X, Q): Q = the same rows of the set -i Y.  Y as for
         inverse (numpy in, numpy out; device tensor in, device tensors out).  The outputs hold NaN before the call; synchronises."""
-        import numpy as np
         import torch
         bt = band_table(bands)
-        if isinstance(Y, np.ndarray):
-            if Y.dtype != np.complex128 or Y.ndim != 2 or Y.shape[1] != self.ncoef or not Y.shape[0]:
-                raise TspwsError(f"Y must be complex128 [nset >= 1][{self.ncoef}], got {Y.dtype} {Y.shape}")
-            Yd = torch.as_tensor(np.ascontiguousarray(Y), device=f"cuda:{self.device}")
-        elif isinstance(Y, torch.Tensor):
-            if Y.dtype != torch.complex128 or Y.dim() != 2 or Y.shape[1] != self.ncoef or not Y.shape[0]:
-                raise TspwsError(f"Y must be complex128 [nset >= 1][{self.ncoef}], got {Y.dtype} {tuple(Y.shape)}")
-            if not Y.is_cuda or (Y.device.index or 0) != self.device or not Y.is_contiguous():
-                raise TspwsError(f"Y must be a contiguous tensor on cuda:{self.device}, got {Y.device}")
-            Yd = Y
-        else:
-            raise TspwsError("Y must be a complex128 numpy array or device tensor")
+        Yd, host = self._coef_sets(Y, "nset")
         R = bt.shape[0]
         X = torch.full((Yd.shape[0], R, self.N), float("nan"), dtype=torch.float64, device=Yd.device)
         Q = torch.full_like(X, float("nan")) if quadrature else None
         check(self.lib.tspws_hip_inverse_bands(self.h, Yd.data_ptr(), Yd.shape[0], bt.ctypes.data, R, X.data_ptr(), Q.data_ptr() if quadrature else None,
                                                self._stream()), "inverse_bands")
         torch.cuda.synchronize(Yd.device)
-        if isinstance(Y, np.ndarray):
+        if host:
             X, Q = X.cpu().numpy(), (Q.cpu().numpy() if quadrature else None)
         return (X, Q) if quadrature else X
 
@@ -407,11 +499,16 @@ class Plan:
 
     # ---- trace-sharded jackknife (see jackknife_sharded) ------------------------------
     @staticmethod
-    def _sel(sel, C_, mtr_global):
+    def _sel(sel, width, noun=None, dims=None):
+        """`sel` as contiguous int8 [rows][width].  With `noun` ("selection" / "masks"; `dims` = its shape in words) only a 2-D int8 / uint8 /
+        bool numpy array passes; without, whatever converts to int8 (the sharded jackknife's callers)."""
         import numpy as np
+        if noun and (not isinstance(sel, np.ndarray) or sel.ndim != 2 or sel.dtype not in (np.int8, np.uint8, np.bool_)):
+            raise TspwsError(f"{noun} must be a 2-D int8 / uint8 / bool numpy array {dims}")
+        rows = sel.shape[0]
         sel = np.ascontiguousarray(sel, dtype=np.int8)
-        if sel.shape != (C_, mtr_global):
-            raise TspwsError(f"selection must be [{C_}][{mtr_global}] (replica x trace of the WHOLE ensemble), got {sel.shape}")
+        if sel.shape != (rows, width):
+            raise TspwsError(f"selection must be [{rows}][{width}] (replica x trace of the WHOLE ensemble), got {sel.shape}")
         return sel
 
     def jackknife_buffer(self, C_):
@@ -426,21 +523,14 @@ class Plan:
     def jackknife_local(self, traces, first, mtr_global, sel):
         """One pass over the shard: its sums for the plain groups (reduce_buffer) and for every replica (jackknife_buffer)."""
         mtr, ld = self._traces(traces)
-        sel = self._sel(sel, sel.shape[0], mtr_global)
+        sel = self._sel(sel, mtr_global)
         check(self.lib.tspws_hip_jackknife_local(self.h, C.byref(self.params), traces.data_ptr(), ld, mtr, first, mtr_global, sel.ctypes.data,
                                                  sel.shape[0], self._stream()), "jackknife_local")
 
     def jackknife_finish(self, mtr_global, sel, c_begin, c_end, ls_out, ts_out, mtr_out):
         """Replicas [c_begin, c_end) from the reduced rows into rows of the [C][N] float32 tensors; sizes into mtr_out (uint32 numpy)."""
-        import torch
-        import numpy as np
-        sel = self._sel(sel, sel.shape[0], mtr_global)
-        if not isinstance(mtr_out, np.ndarray) or mtr_out.dtype != np.uint32 or mtr_out.shape != (sel.shape[0],) or not mtr_out.flags.c_contiguous:
-            raise TspwsError(f"mtr_out must be a contiguous uint32 numpy array of {sel.shape[0]} entries")
-        for t, name in ((ls_out, "ls_out"), (ts_out, "ts_out")):
-            if t.dtype != torch.float32 or tuple(t.shape) != (sel.shape[0], self.N) or not t.is_contiguous() or not t.is_cuda or \
-                    (t.device.index or 0) != self.device:
-                raise TspwsError(f"{name} must be a contiguous float32 [{sel.shape[0]}][{self.N}] tensor on cuda:{self.device}")
+        sel = self._sel(sel, mtr_global)
+        self._rows_out((sel.shape[0],), None, ls_out, ts_out, mtr_out, new=None)
         check(self.lib.tspws_hip_jackknife_finish(self.h, C.byref(self.params), mtr_global, sel.ctypes.data, sel.shape[0], c_begin, c_end,
                                                   ls_out.data_ptr(), ts_out.data_ptr(), mtr_out.ctypes.data, self._stream()), "jackknife_finish")
 
@@ -456,17 +546,13 @@ class Plan:
 
     def stack_finish_scales(self, mtr_global, s_begin, s_end, x2):
         """This rank's share of the finish stage: x2 (float64 [2 N], cuda) receives the partial reconstructions of the scales."""
-        import torch
-        if x2.dtype != torch.float64 or x2.numel() != 2 * self.N or not x2.is_contiguous() or not x2.is_cuda or (x2.device.index or 0) != self.device:
-            raise TspwsError(f"x2 must be a contiguous float64 tensor of {2 * self.N} values on cuda:{self.device}")
+        self._need(x2, "x2", "float64", 2 * self.N, "tensor of {} values", exact=True)
         check(self.lib.tspws_hip_stack_finish_scales(self.h, C.byref(self.params), mtr_global, s_begin, s_end, x2.data_ptr(), self._stream()),
               "stack_finish_scales")
 
     def epilogue(self, x2, mtr_global, ls, ts):
         """ls = (float)x2[N:] / mtr, ts = (float)x2[:N]  (reference epilogue, ts_pws1f_lib.c:233-241)."""
-        import torch
-        if x2.dtype != torch.float64 or x2.numel() != 2 * self.N or not x2.is_contiguous() or not x2.is_cuda or (x2.device.index or 0) != self.device:
-            raise TspwsError(f"x2 must be a contiguous float64 tensor of {2 * self.N} values on cuda:{self.device}")
+        self._need(x2, "x2", "float64", 2 * self.N, "tensor of {} values", exact=True)
         check(self.lib.tspws_hip_epilogue(self._out(ls, "ls"), self._out(ts, "ts"), x2.data_ptr() + 8 * self.N, x2.data_ptr(), self.N, mtr_global,
                                           self._stream()), "epilogue")
 
@@ -480,7 +566,7 @@ class Plan:
         import numpy as np
         import torch
         mtr, ld = self._traces(traces)
-        sel = self._sel(sel, sel.shape[0], mtr)
+        sel = self._sel(sel, mtr)
         Cn = sel.shape[0]
         ls = torch.empty(self.N, dtype=torch.float32, device=traces.device) if ls is None else ls
         ts = torch.empty(self.N, dtype=torch.float32, device=traces.device) if ts is None else ts
@@ -495,22 +581,10 @@ class Plan:
     def jackknife_single(self, traces, sel, ls_out=None, ts_out=None, mtr_out=None):
         """Single-stage jackknife replicas (tspws_hip_jackknife_single; the reference leaves these rows untouched).
         `sel` = [C][mtr] int8 selection (jackknife_selection).  Returns ls_out[C][N], ts_out[C][N] (float32 cuda), mtr_out[C] (uint32)."""
-        import numpy as np
-        import torch
         mtr, ld = self._traces(traces)
-        if not isinstance(sel, np.ndarray) or sel.ndim != 2 or sel.dtype not in (np.int8, np.uint8, np.bool_):
-            raise TspwsError("selection must be a 2-D int8 / uint8 / bool numpy array [C][mtr]")
-        sel = self._sel(sel, sel.shape[0], mtr)
+        sel = self._sel(sel, mtr, "selection", "[C][mtr]")
         Cn = sel.shape[0]
-        ls_out = torch.empty((Cn, self.N), dtype=torch.float32, device=traces.device) if ls_out is None else ls_out
-        ts_out = torch.empty((Cn, self.N), dtype=torch.float32, device=traces.device) if ts_out is None else ts_out
-        mtr_out = np.zeros(Cn, np.uint32) if mtr_out is None else mtr_out
-        if not isinstance(mtr_out, np.ndarray) or mtr_out.dtype != np.uint32 or mtr_out.shape != (Cn,) or not mtr_out.flags.c_contiguous:
-            raise TspwsError(f"mtr_out must be a contiguous uint32 numpy array of {Cn} entries")
-        for t, name in ((ls_out, "ls_out"), (ts_out, "ts_out")):
-            if t.dtype != torch.float32 or tuple(t.shape) != (Cn, self.N) or not t.is_contiguous() or not t.is_cuda or \
-                    (t.device.index or 0) != self.device:
-                raise TspwsError(f"{name} must be a contiguous float32 [{Cn}][{self.N}] tensor on cuda:{self.device}")
+        ls_out, ts_out, mtr_out = self._rows_out((Cn,), traces.device, ls_out, ts_out, mtr_out)
         check(self.lib.tspws_hip_jackknife_single(self.h, C.byref(self.params), traces.data_ptr(), ld, mtr, sel.ctypes.data, Cn, ls_out.data_ptr(),
                                                   ts_out.data_ptr(), mtr_out.ctypes.data, self._stream()), "jackknife_single")
         return ls_out, ts_out, mtr_out
@@ -542,22 +616,13 @@ class Plan:
         """B ensembles of one trace array in ONE call (tspws_hip_stack_batch): ensemble b = rows [first[b], first[b+1]) of the float32
         [mtr][N] device tensor `traces`; `first` = B + 1 non-decreasing integer offsets (first[0] may be > 0).  Returns ls[B][N], ts[B][N]
         (float32 cuda): row b = what stack_single gives for ensemble b (an empty ensemble: zero rows)."""
-        import numpy as np
         import torch
         mtr, ld = self._traces(traces)
-        f = np.asarray(first)
-        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
-            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
-        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
-            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
-        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
-        B = f.size - 1
+        f, B, _ = _offsets(first, mtr)
         ls = torch.empty((B, self.N), dtype=torch.float32, device=traces.device) if ls is None else ls
         ts = torch.empty((B, self.N), dtype=torch.float32, device=traces.device) if ts is None else ts
-        for t, name in ((ls, "ls"), (ts, "ts")):
-            if t.dtype != torch.float32 or tuple(t.shape) != (B, self.N) or not t.is_contiguous() or not t.is_cuda or \
-                    (t.device.index or 0) != self.device:
-                raise TspwsError(f"{name} must be a contiguous float32 [{B}][{self.N}] tensor on cuda:{self.device}")
+        self._need(ls, "ls", "float32", (B, self.N))
+        self._need(ts, "ts", "float32", (B, self.N))
         check(self.lib.tspws_hip_stack_batch(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, ls.data_ptr(), ts.data_ptr(),
                                              self._stream()), "stack_batch")
         return ls, ts
@@ -567,17 +632,11 @@ class Plan:
         makes them from frequency edges).  Returns ls[B][R][N], ts[B][R][N] (float32 cuda) -- row (b, r) = band r's share of ensemble b's
         linear stack and ts-PWS -- and, with envelope=True, also ls_env, ts_env: the envelopes hypot(row, its quadrature).  B = 1 is the
         single-ensemble call.  Empty ensembles and empty bands give zero rows."""
-        import numpy as np
         import torch
         mtr, ld = self._traces(traces)
-        f = np.asarray(first)
-        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
-            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
-        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
-            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
-        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
+        f, B, _ = _offsets(first, mtr)
         bt = band_table(bands)
-        B, R = f.size - 1, bt.shape[0]
+        R = bt.shape[0]
         outs = [torch.full((B, R, self.N), float("nan"), dtype=torch.float32, device=traces.device) for _ in range(4 if envelope else 2)]
         ptr = [t.data_ptr() for t in outs] + [None] * (4 - len(outs))
         check(self.lib.tspws_hip_stack_batch_bands(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, bt.ctypes.data, R, *ptr,
@@ -587,50 +646,28 @@ class Plan:
     def stack_batch_bands_stats(self):
         """The last stack_batch_bands call with B > 0 and R > 0 (tspws_hip_stack_batch_bands_stats): batch_stats' counts, the batches of
         sets of its band finish, the scales with work items and whether the quadrature ran."""
-        st = (C.c_uint * 9)()
-        check(self.lib.tspws_hip_stack_batch_bands_stats(self.h, C.byref(st)), "stack_batch_bands_stats")
-        return dict(zip(("single_pass", "two_stage_pass", "looped", "empty", "rounds", "pass_batches", "finish_batches", "scales", "quadrature"), list(st)))
+        return self._stats("stack_batch_bands_stats", ("single_pass", "two_stage_pass", "looped", "empty", "rounds", "pass_batches", "finish_batches", "scales", "quadrature"))
 
     def batch_stats(self):
         """How the last stack_batch call with B > 0 stacked its ensembles (tspws_hip_stack_batch_stats): dict of counts."""
-        st = (C.c_uint * 6)()
-        check(self.lib.tspws_hip_stack_batch_stats(self.h, C.byref(st)), "stack_batch_stats")
-        return dict(zip(("single_pass", "two_stage_pass", "looped", "empty", "rounds", "pass_batches"), list(st)))
+        return self._stats("stack_batch_stats", ("single_pass", "two_stage_pass", "looped", "empty", "rounds", "pass_batches"))
 
     def _jackknife_batch(self, what, traces, first, sel, ls, ts, ls_out, ts_out, mtr_out, main):
         """Argument checks, output allocation and the call of the batched jackknives (tspws_hip_<what>)."""
-        import numpy as np
         import torch
         mtr, ld = self._traces(traces)
-        f = np.asarray(first)
-        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
-            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
-        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
-            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
-        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
-        B, T = f.size - 1, int(f[-1] - f[0])
-        if not isinstance(sel, np.ndarray) or sel.ndim != 2 or sel.dtype not in (np.int8, np.uint8, np.bool_):
-            raise TspwsError("selection must be a 2-D int8 / uint8 / bool numpy array [C][T]")
-        sel = self._sel(sel, sel.shape[0], T)
+        f, B, T = _offsets(first, mtr)
+        sel = self._sel(sel, T, "selection", "[C][T]")
         Cn = sel.shape[0]
         dev = traces.device
+        ls_out, ts_out, mtr_out = self._rows_out((B, Cn), dev, ls_out, ts_out, mtr_out, what=f"{[B, Cn, self.N]} tensor")
         if main:
             ls = torch.empty((B, self.N), dtype=torch.float32, device=dev) if ls is None else ls
             ts = torch.empty((B, self.N), dtype=torch.float32, device=dev) if ts is None else ts
+            self._need(ls, "ls", "float32", (B, self.N), f"{[B, self.N]} tensor")
+            self._need(ts, "ts", "float32", (B, self.N), f"{[B, self.N]} tensor")
         elif ls is not None or ts is not None:
             raise TspwsError("main=False takes no ls / ts")
-        ls_out = torch.empty((B, Cn, self.N), dtype=torch.float32, device=dev) if ls_out is None else ls_out
-        ts_out = torch.empty((B, Cn, self.N), dtype=torch.float32, device=dev) if ts_out is None else ts_out
-        mtr_out = np.zeros((B, Cn), np.uint32) if mtr_out is None else mtr_out
-        if not isinstance(mtr_out, np.ndarray) or mtr_out.dtype != np.uint32 or mtr_out.shape != (B, Cn) or not mtr_out.flags.c_contiguous:
-            raise TspwsError(f"mtr_out must be a contiguous uint32 numpy array [{B}][{Cn}]")
-        checks = [(ls_out, "ls_out", (B, Cn, self.N)), (ts_out, "ts_out", (B, Cn, self.N))]
-        if main:
-            checks += [(ls, "ls", (B, self.N)), (ts, "ts", (B, self.N))]
-        for t, name, shape in checks:
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda or \
-                    (t.device.index or 0) != self.device:
-                raise TspwsError(f"{name} must be a contiguous float32 {list(shape)} tensor on cuda:{self.device}")
         check(getattr(self.lib, "tspws_hip_" + what)(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, sel.ctypes.data, Cn,
                                                      ls.data_ptr() if main else None, ts.data_ptr() if main else None, ls_out.data_ptr(),
                                                      ts_out.data_ptr(), mtr_out.ctypes.data, self._stream()), what)
@@ -646,9 +683,7 @@ class Plan:
 
     def jackknife_batch_stats(self):
         """How the last jackknife_batch call with B > 0 and C > 0 went (tspws_hip_jackknife_batch_stats): dict of counts."""
-        st = (C.c_uint * 6)()
-        check(self.lib.tspws_hip_jackknife_batch_stats(self.h, C.byref(st)), "jackknife_batch_stats")
-        return dict(zip(("shared", "looped", "empty", "rounds", "pass_batches", "classes"), list(st)))
+        return self._stats("jackknife_batch_stats", ("shared", "looped", "empty", "rounds", "pass_batches", "classes"))
 
     def jackknife_batch_two_stage(self, traces, first, sel, ls=None, ts=None, ls_out=None, ts_out=None, mtr_out=None, main=True):
         """Two-stage jackknife of B ensembles of one trace array in ONE call (tspws_hip_jackknife_batch_two_stage); arguments and return
@@ -659,30 +694,19 @@ class Plan:
 
     def jackknife_batch_two_stage_stats(self):
         """How the last jackknife_batch_two_stage call with B > 0 and C > 0 went (tspws_hip_jackknife_batch_two_stage_stats): dict of counts."""
-        st = (C.c_uint * 6)()
-        check(self.lib.tspws_hip_jackknife_batch_two_stage_stats(self.h, C.byref(st)), "jackknife_batch_two_stage_stats")
-        return dict(zip(("shared", "looped", "empty", "rounds", "tiles", "rows"), list(st)))
+        return self._stats("jackknife_batch_two_stage_stats", ("shared", "looped", "empty", "rounds", "tiles", "rows"))
 
     def subsample_sel(self, traces, sel, prob=None, ls_out=None, ts_out=None):
         """The random subsamples of ONE ensemble with the masks given (tspws_hip_subsample_sel): `sel` = [M][mtr] int8 masks (1 = kept), every
         row with K = ceil(mtr * subsmpl_p) ones (`prob` replaces the plan's subsmpl_p for this call).  Returns ls_out[M][N], ts_out[M][N]
         (float32 cuda; given or new).  Synchronises."""
-        import numpy as np
-        import torch
         mtr, ld = self._traces(traces)
-        if not isinstance(sel, np.ndarray) or sel.ndim != 2 or sel.dtype not in (np.int8, np.uint8, np.bool_):
-            raise TspwsError("masks must be a 2-D int8 / uint8 / bool numpy array [M][mtr]")
-        sel = self._sel(sel, sel.shape[0], mtr)
+        sel = self._sel(sel, mtr, "masks", "[M][mtr]")
         Mn = sel.shape[0]
         p = t_tsPWS.from_buffer_copy(self.params)
         if prob is not None:
             p.subsmpl_p = prob
-        ls_out = torch.zeros((Mn, self.N), dtype=torch.float32, device=traces.device) if ls_out is None else ls_out
-        ts_out = torch.zeros((Mn, self.N), dtype=torch.float32, device=traces.device) if ts_out is None else ts_out
-        for t, name in ((ls_out, "ls_out"), (ts_out, "ts_out")):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (Mn, self.N) or not t.is_contiguous() or \
-                    not t.is_cuda or (t.device.index or 0) != self.device:
-                raise TspwsError(f"{name} must be a contiguous float32 [{Mn}][{self.N}] tensor on cuda:{self.device}")
+        ls_out, ts_out, _ = self._rows_out((Mn,), traces.device, ls_out, ts_out, counts=False, new="zeros")
         check(self.lib.tspws_hip_subsample_sel(self.h, C.byref(p), traces.data_ptr(), ld, mtr, Mn, sel.ctypes.data, ls_out.data_ptr(), ts_out.data_ptr(),
                                                self._stream()), "subsample_sel")
         return ls_out, ts_out
@@ -693,39 +717,18 @@ class Plan:
         T = first[B] - first[0], column i - first[0] for trace i (subsampling_selection_batch draws them).  Returns ls_out[B][M][N],
         ts_out[B][M][N] (float32 cuda) and mtr_out[B][M] (uint32, the traces every row keeps): block b = what subsample_sel gives for ensemble b
         alone (a row that keeps nothing and an empty ensemble: zero rows, count 0).  Synchronises."""
-        import numpy as np
-        import torch
         mtr, ld = self._traces(traces)
-        f = np.asarray(first)
-        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
-            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
-        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
-            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
-        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
-        B, T = f.size - 1, int(f[-1] - f[0])
-        if not isinstance(sel, np.ndarray) or sel.ndim != 2 or sel.dtype not in (np.int8, np.uint8, np.bool_):
-            raise TspwsError("masks must be a 2-D int8 / uint8 / bool numpy array [M][T]")
-        sel = self._sel(sel, sel.shape[0], T)
+        f, B, T = _offsets(first, mtr)
+        sel = self._sel(sel, T, "masks", "[M][T]")
         Mn = sel.shape[0]
-        dev = traces.device
-        ls_out = torch.empty((B, Mn, self.N), dtype=torch.float32, device=dev) if ls_out is None else ls_out
-        ts_out = torch.empty((B, Mn, self.N), dtype=torch.float32, device=dev) if ts_out is None else ts_out
-        mtr_out = np.zeros((B, Mn), np.uint32) if mtr_out is None else mtr_out
-        if not isinstance(mtr_out, np.ndarray) or mtr_out.dtype != np.uint32 or mtr_out.shape != (B, Mn) or not mtr_out.flags.c_contiguous:
-            raise TspwsError(f"mtr_out must be a contiguous uint32 numpy array [{B}][{Mn}]")
-        for t, name in ((ls_out, "ls_out"), (ts_out, "ts_out")):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (B, Mn, self.N) or not t.is_contiguous() or \
-                    not t.is_cuda or (t.device.index or 0) != self.device:
-                raise TspwsError(f"{name} must be a contiguous float32 [{B}][{Mn}][{self.N}] tensor on cuda:{self.device}")
+        ls_out, ts_out, mtr_out = self._rows_out((B, Mn), traces.device, ls_out, ts_out, mtr_out)
         check(self.lib.tspws_hip_subsample_batch_sel(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, Mn, sel.ctypes.data,
                                                      ls_out.data_ptr(), ts_out.data_ptr(), mtr_out.ctypes.data, self._stream()), "subsample_batch_sel")
         return ls_out, ts_out, mtr_out
 
     def subsample_batch_stats(self):
         """How the last subsample_batch call with B > 0 and M > 0 went (tspws_hip_subsample_batch_stats): dict of counts."""
-        st = (C.c_uint * 6)()
-        check(self.lib.tspws_hip_subsample_batch_stats(self.h, C.byref(st)), "subsample_batch_stats")
-        return dict(zip(("single_shared", "two_stage_shared", "looped", "empty", "rounds", "rows"), list(st)))
+        return self._stats("subsample_batch_stats", ("single_shared", "two_stage_shared", "looped", "empty", "rounds", "rows"))
 
     def bootstrap_batch(self, traces, first, cnt, ls_out=None, ts_out=None, mtr_out=None, stats=False):
         """M bootstrap replicas of each of B single-stage ensembles of one trace array in ONE call (tspws_hip_bootstrap_batch_cnt): ensemble
@@ -739,30 +742,15 @@ class Plan:
         import numpy as np
         import torch
         mtr, ld = self._traces(traces)
-        f = np.asarray(first)
-        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
-            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
-        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
-            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
-        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
-        B, T = f.size - 1, int(f[-1] - f[0])
+        f, B, T = _offsets(first, mtr)
         if not isinstance(cnt, np.ndarray) or cnt.ndim != 2 or cnt.dtype != np.uint8:
             raise TspwsError("counts must be a 2-D uint8 numpy array [M][T]")
         if cnt.shape[1] != T:
             raise TspwsError(f"counts must be [M][{T}] (replica x trace of the batch), got {cnt.shape}")
         cnt = np.ascontiguousarray(cnt)
         Mn = cnt.shape[0]
-        dev = traces.device
-        ls_out = torch.empty((B, Mn, self.N), dtype=torch.float32, device=dev) if ls_out is None else ls_out
-        ts_out = torch.empty((B, Mn, self.N), dtype=torch.float32, device=dev) if ts_out is None else ts_out
-        mtr_out = np.zeros((B, Mn), np.uint32) if mtr_out is None else mtr_out
-        if not isinstance(mtr_out, np.ndarray) or mtr_out.dtype != np.uint32 or mtr_out.shape != (B, Mn) or not mtr_out.flags.c_contiguous:
-            raise TspwsError(f"mtr_out must be a contiguous uint32 numpy array [{B}][{Mn}]")
-        for t, name in ((ls_out, "ls_out"), (ts_out, "ts_out")):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (B, Mn, self.N) or not t.is_contiguous() or \
-                    not t.is_cuda or (t.device.index or 0) != self.device:
-                raise TspwsError(f"{name} must be a contiguous float32 [{B}][{Mn}][{self.N}] tensor on cuda:{self.device}")
-        st = torch.empty((B, 4, self.N), dtype=torch.float32, device=dev) if stats else None
+        ls_out, ts_out, mtr_out = self._rows_out((B, Mn), traces.device, ls_out, ts_out, mtr_out)
+        st = torch.empty((B, 4, self.N), dtype=torch.float32, device=traces.device) if stats else None
         check(self.lib.tspws_hip_bootstrap_batch_cnt(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, Mn, cnt.ctypes.data,
                                                      ls_out.data_ptr(), ts_out.data_ptr(), mtr_out.ctypes.data, st.data_ptr() if stats else None,
                                                      self._stream()), "bootstrap_batch_cnt")
@@ -770,9 +758,7 @@ class Plan:
 
     def bootstrap_batch_stats(self):
         """How the last bootstrap_batch call with B > 0 and M > 0 went (tspws_hip_bootstrap_batch_stats): dict of counts."""
-        st = (C.c_uint * 5)()
-        check(self.lib.tspws_hip_bootstrap_batch_stats(self.h, C.byref(st)), "bootstrap_batch_stats")
-        return dict(zip(("shared", "empty", "rounds", "rows", "max_count"), list(st)))
+        return self._stats("bootstrap_batch_stats", ("shared", "empty", "rounds", "rows", "max_count"))
 
     def weighted_stack_batch(self, traces, first, w, ls_out=None, ts_out=None, mtr_out=None):
         """M real-weighted stacks of each of B single-stage ensembles of one trace array in ONE call (tspws_hip_weighted_stack_batch): ensemble
@@ -784,31 +770,15 @@ class Plan:
         row on that mask, bit for bit.  NaN, infinite and negative weights and two-stage ensembles (0 < Kmax <= traces) are refused.
         Synchronises."""
         import numpy as np
-        import torch
         mtr, ld = self._traces(traces)
-        f = np.asarray(first)
-        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
-            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
-        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
-            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
-        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
-        B, T = f.size - 1, int(f[-1] - f[0])
+        f, B, T = _offsets(first, mtr)
         if not isinstance(w, np.ndarray) or w.ndim != 2 or w.dtype != np.float64:
             raise TspwsError("weights must be a 2-D float64 numpy array [M][T]")
         if w.shape[1] != T:
             raise TspwsError(f"weights must be [M][{T}] (row x trace of the batch), got {w.shape}")
         w = np.ascontiguousarray(w)
         Mn = w.shape[0]
-        dev = traces.device
-        ls_out = torch.empty((B, Mn, self.N), dtype=torch.float32, device=dev) if ls_out is None else ls_out
-        ts_out = torch.empty((B, Mn, self.N), dtype=torch.float32, device=dev) if ts_out is None else ts_out
-        mtr_out = np.zeros((B, Mn), np.uint32) if mtr_out is None else mtr_out
-        if not isinstance(mtr_out, np.ndarray) or mtr_out.dtype != np.uint32 or mtr_out.shape != (B, Mn) or not mtr_out.flags.c_contiguous:
-            raise TspwsError(f"mtr_out must be a contiguous uint32 numpy array [{B}][{Mn}]")
-        for t, name in ((ls_out, "ls_out"), (ts_out, "ts_out")):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (B, Mn, self.N) or not t.is_contiguous() or \
-                    not t.is_cuda or (t.device.index or 0) != self.device:
-                raise TspwsError(f"{name} must be a contiguous float32 [{B}][{Mn}][{self.N}] tensor on cuda:{self.device}")
+        ls_out, ts_out, mtr_out = self._rows_out((B, Mn), traces.device, ls_out, ts_out, mtr_out)
         keff = np.zeros((B, Mn), np.float64)
         check(self.lib.tspws_hip_weighted_stack_batch(self.h, C.byref(self.params), traces.data_ptr(), ld, f.ctypes.data, B, Mn, w.ctypes.data,
                                                       ls_out.data_ptr(), ts_out.data_ptr(), mtr_out.ctypes.data, keff.ctypes.data, self._stream()),
@@ -817,9 +787,7 @@ class Plan:
 
     def weighted_stack_batch_stats(self):
         """How the last weighted_stack_batch call with B > 0 and M > 0 went (tspws_hip_weighted_stack_batch_stats): dict of counts."""
-        st = (C.c_uint * 4)()
-        check(self.lib.tspws_hip_weighted_stack_batch_stats(self.h, C.byref(st)), "weighted_stack_batch_stats")
-        return dict(zip(("shared", "empty", "rounds", "rows"), list(st)))
+        return self._stats("weighted_stack_batch_stats", ("shared", "empty", "rounds", "rows"))
 
     def replica_bands(self, rows, q, mtr=None, out=None):
         """Per sample, the quantiles `q` (a sequence of at most 8 probabilities in [0, 1]) over the replicas of each of B ensembles
@@ -829,19 +797,7 @@ class Plan:
         replicas, computed in FP64 from the exact order statistics; no participating replica gives zero bands.  Synchronises."""
         import numpy as np
         import torch
-        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[2] != self.N:
-            raise TspwsError(f"rows must be a float32 [B][M][{self.N}] tensor, got {getattr(rows, 'dtype', type(rows))} {tuple(getattr(rows, 'shape', ()))}")
-        if not rows.is_cuda or (rows.device.index or 0) != self.device:
-            raise TspwsError(f"rows live on {rows.device}, the plan on cuda:{self.device}")
-        B, Mn = rows.shape[0], rows.shape[1]
-        ld = rows.stride(1) if Mn > 1 else (rows.stride(0) if B > 1 else self.N)
-        if B and Mn:
-            if rows.stride(2) != 1:
-                raise TspwsError("rows must be contiguous along the samples (stride(2) == 1)")
-            if ld < self.N:
-                raise TspwsError("overlapping replica rows (row stride < N)")
-            if B > 1 and rows.stride(0) != Mn * ld:
-                raise TspwsError("rows must be a [B][M][N] view of one [B][M][ld] base (stride(0) == M * stride(1))")
+        B, Mn, ld = self._strided_rows(rows, kind="replica ")
         try:
             qa = np.ascontiguousarray(np.asarray(q, dtype=np.float64))
         except (TypeError, ValueError):
@@ -849,14 +805,9 @@ class Plan:
         if qa.ndim != 1:
             raise TspwsError("q must be a sequence of floats")
         Q = qa.size
-        if mtr is not None:
-            if not isinstance(mtr, np.ndarray) or mtr.dtype != np.uint32 or mtr.shape != (B, Mn):
-                raise TspwsError(f"mtr must be None or a uint32 numpy array [{B}][{Mn}]")
-            mtr = np.ascontiguousarray(mtr)
+        mtr = _host_array(mtr, "mtr", np.uint32, (B, Mn), optional=True)
         out = torch.empty((B, Q, self.N), dtype=torch.float32, device=rows.device) if out is None else out
-        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B, Q, self.N) or not out.is_contiguous() or \
-                not out.is_cuda or (out.device.index or 0) != self.device:
-            raise TspwsError(f"out must be a contiguous float32 [{B}][{Q}][{self.N}] tensor on cuda:{self.device}")
+        self._need(out, "out", "float32", (B, Q, self.N))
         check(self.lib.tspws_hip_replica_bands(self.h, rows.data_ptr(), ld, B, Mn, mtr.ctypes.data if mtr is not None else None, qa.ctypes.data, Q,
                                                out.data_ptr(), self._stream()), "replica_bands")
         return out
@@ -864,20 +815,7 @@ class Plan:
     def replica_bands_stats(self):
         """How the last replica_bands call with B, M, Q > 0 went (tspws_hip_replica_bands_stats): dict of counts; lds_max_rows = the largest
         M whose replicas are selected from LDS."""
-        st = (C.c_uint * 5)()
-        check(self.lib.tspws_hip_replica_bands_stats(self.h, C.byref(st)), "replica_bands_stats")
-        return dict(zip(("lds", "global", "empty", "rounds", "lds_max_rows"), list(st)))
-
-    def _first(self, first, mtr):
-        """(first as contiguous uint64, B, T) of B + 1 ensemble offsets into `mtr` trace rows."""
-        import numpy as np
-        f = np.asarray(first)
-        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
-            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
-        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
-            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
-        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
-        return f, f.size - 1, int(f[-1] - f[0])
+        return self._stats("replica_bands_stats", ("lds", "global", "empty", "rounds", "lds_max_rows"))
 
     def _window(self, window):
         """(n0, n1) of a lag window: None = the whole trace, else n0 <= n < n1 (n1 == 0: the trace length)."""
@@ -897,25 +835,16 @@ class Plan:
         energies, float64 cuda [T].  The outputs hold NaN before the call (an unwritten entry shows).  Synchronises."""
         import torch
         mtr, ld = self._traces(traces)
-        f, B, T = self._first(first, mtr)
+        f, B, T = _offsets(first, mtr)
         if not isinstance(refs, torch.Tensor) or refs.dtype != torch.float32 or refs.dim() not in (2, 3) or refs.shape[-1] != self.N or refs.shape[0] != B:
             raise TspwsError(f"refs must be a float32 [{B}][R][{self.N}] or [{B}][{self.N}] tensor, got {getattr(refs, 'dtype', type(refs))} "
                              f"{tuple(getattr(refs, 'shape', ()))}")
-        if not refs.is_cuda or (refs.device.index or 0) != self.device:
-            raise TspwsError(f"refs live on {refs.device}, the plan on cuda:{self.device}")
         if refs.dim() == 2:
             refs = refs.unsqueeze(1)
         R = refs.shape[1]
         if not 1 <= R <= 4:
             raise TspwsError(f"1 to 4 reference rows per ensemble, got {R}")
-        ldr = refs.stride(1) if R > 1 else (refs.stride(0) if B > 1 else self.N)
-        if B:
-            if refs.stride(2) != 1:
-                raise TspwsError("refs must be contiguous along the samples (stride(2) == 1)")
-            if ldr < self.N:
-                raise TspwsError("overlapping reference rows (row stride < N)")
-            if B > 1 and refs.stride(0) != R * ldr:
-                raise TspwsError("refs must be a [B][R][N] view of one [B][R][ld] base (stride(0) == R * stride(1))")
+        _, _, ldr = self._strided_rows(refs, "refs", "reference ", "R")
         n0, n1 = self._window(window)
         scores = torch.full((R, 3, T), float("nan"), dtype=torch.float64, device=traces.device)
         en = torch.full((T,), float("nan"), dtype=torch.float64, device=traces.device) if energy else None
@@ -927,9 +856,7 @@ class Plan:
 
     def trace_scores_stats(self):
         """How the last trace_scores call with traces went (tspws_hip_trace_scores_stats): dict(vec, segments, rounds, empty)."""
-        st = (C.c_uint * 4)()
-        check(self.lib.tspws_hip_trace_scores_stats(self.h, C.byref(st)), "trace_scores_stats")
-        return dict(zip(("vec", "segments", "rounds", "empty"), list(st)))
+        return self._stats("trace_scores_stats", ("vec", "segments", "rounds", "empty"))
 
     def selective_stack_batch(self, traces, first, against="ts", rule="mad", a=3.0, iters=2, window=None):
         """The selective stack of B ensembles (tspws_hip_selective_stack_batch): stack, score every trace against the ensemble's own
@@ -940,7 +867,7 @@ class Plan:
         import numpy as np
         import torch
         mtr, ld = self._traces(traces)
-        f, B, T = self._first(first, mtr)
+        f, B, T = _offsets(first, mtr)
         if against not in AGAINST or rule not in RULES:
             raise TspwsError(f"against must be one of {tuple(AGAINST)} and rule one of {tuple(RULES)}, got {against!r}, {rule!r}")
         n0, n1 = self._window(window)
@@ -965,19 +892,7 @@ class Plan:
         returned as given.  New outputs hold NaN before the call.  Synchronises."""
         import numpy as np
         import torch
-        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[2] != self.N:
-            raise TspwsError(f"rows must be a float32 [B][M][{self.N}] tensor, got {getattr(rows, 'dtype', type(rows))} {tuple(getattr(rows, 'shape', ()))}")
-        if not rows.is_cuda or (rows.device.index or 0) != self.device:
-            raise TspwsError(f"rows live on {rows.device}, the plan on cuda:{self.device}")
-        B, Mn = rows.shape[0], rows.shape[1]
-        ld = rows.stride(1) if Mn > 1 else (rows.stride(0) if B > 1 else self.N)
-        if B and Mn:
-            if rows.stride(2) != 1:
-                raise TspwsError("rows must be contiguous along the samples (stride(2) == 1)")
-            if ld < self.N:
-                raise TspwsError("overlapping rows (row stride < N)")
-            if B > 1 and rows.stride(0) != Mn * ld:
-                raise TspwsError("rows must be a [B][M][N] view of one [B][M][ld] base (stride(0) == M * stride(1))")
+        B, Mn, ld = self._strided_rows(rows)
         if not isinstance(ref, torch.Tensor) or ref.dtype != torch.float32 or tuple(ref.shape) != (B, self.N):
             raise TspwsError(f"ref must be a float32 [{B}][{self.N}] tensor, got {getattr(ref, 'dtype', type(ref))} {tuple(getattr(ref, 'shape', ()))}")
         if not ref.is_cuda or (ref.device.index or 0) != self.device:
@@ -994,20 +909,14 @@ class Plan:
             raise TspwsError("eps must be a sequence of floats, windows a sequence of (n0, n1) pairs of non-negative integers")
         wa = np.ascontiguousarray(wa, dtype=np.uint64)  # size_t
         E, W = ea.size, wa.shape[0]
-        if mtr is not None:
-            if not isinstance(mtr, np.ndarray) or mtr.dtype != np.uint32 or mtr.shape != (B, Mn):
-                raise TspwsError(f"mtr must be None or a uint32 numpy array [{B}][{Mn}]")
-            mtr = np.ascontiguousarray(mtr)
+        mtr = _host_array(mtr, "mtr", np.uint32, (B, Mn), optional=True)
         o_cc, o_fit = (out if cc else (None, out)) if out is not None else (None, None)
         if out is None:
             o_fit = torch.full((B, Mn, W, 4), float("nan"), dtype=torch.float64, device=rows.device)
             o_cc = torch.full((B, Mn, W, E), float("nan"), dtype=torch.float64, device=rows.device) if cc else None
-        for t, n, name in ((o_fit, 4, "fit"), (o_cc, E, "cc")):
-            if t is None and name == "cc" and not cc:
-                continue
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.numel() < B * Mn * W * n or not t.is_contiguous() or not t.is_cuda or \
-                    (t.device.index or 0) != self.device:
-                raise TspwsError(f"out: {name} must be a contiguous float64 tensor of >= {B * Mn * W * n} values on cuda:{self.device}")
+        self._need(o_fit, "out: fit", "float64", B * Mn * W * 4, "tensor of >= {} values")
+        if cc:
+            self._need(o_cc, "out: cc", "float64", B * Mn * W * E, "tensor of >= {} values")
         if B and Mn:  # (an empty tensor has no address)
             check(self.lib.tspws_hip_stretch_rows(self.h, rows.data_ptr(), ld, B, Mn, mtr.ctypes.data if mtr is not None else None, ref.data_ptr(), ldr,
                                                   float(z), ea.ctypes.data, E, wa.ctypes.data, W, o_cc.data_ptr() if cc else None, o_fit.data_ptr(),
@@ -1016,17 +925,7 @@ class Plan:
 
     def stretch_rows_stats(self):
         """How the last stretch_rows call with B, M > 0 went (tspws_hip_stretch_rows_stats): dict(rounds, segments, rows, left_out, chunks)."""
-        st = (C.c_uint * 5)()
-        check(self.lib.tspws_hip_stretch_rows_stats(self.h, C.byref(st)), "stretch_rows_stats")
-        return dict(zip(("rounds", "segments", "rows", "left_out", "chunks"), list(st)))
-
-    def _refs(self, t, name, rows):
-        """Data pointer of a reference array: contiguous float32 [rows][N] (or [N] for one row) on the plan's device."""
-        import torch
-        ok = isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda and (t.device.index or 0) == self.device
-        if not ok or (tuple(t.shape) != (rows, self.N) and not (rows == 1 and tuple(t.shape) == (self.N,))):
-            raise TspwsError(f"{name} must be a contiguous float32 [{rows}][{self.N}] tensor on cuda:{self.device}")
-        return t.data_ptr()
+        return self._stats("stretch_rows_stats", ("rounds", "segments", "rows", "left_out", "chunks"))
 
     def convergence(self, traces, ref_ts, ref_ls, steps=False):
         """Convergence curves of ONE ensemble (tspws_hip_convergence) on device tensors: `traces` float32 [mtr][N], `ref_ts` / `ref_ls`
@@ -1052,13 +951,7 @@ class Plan:
         import numpy as np
         import torch
         mtr, ld = self._traces(traces)
-        f = np.asarray(first)
-        if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
-            raise TspwsError("first must be a 1-D integer array of B + 1 ensemble offsets")
-        if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > mtr:
-            raise TspwsError(f"first must be non-decreasing offsets into the {mtr} trace rows")
-        f = np.ascontiguousarray(f, dtype=np.uint64)  # size_t
-        B, T = f.size - 1, int(f[-1] - f[0])
+        f, B, T = _offsets(first, mtr)
         if (ref_ts is None) != (ref_ls is None):
             raise TspwsError("ref_ts and ref_ls are given together or not at all")
         if ref_ts is None:
@@ -1073,9 +966,7 @@ class Plan:
 
     def convergence_batch_stats(self):
         """How the last convergence_batch call with traces went (tspws_hip_convergence_batch_stats): dict of counts."""
-        st = (C.c_uint * 6)()
-        check(self.lib.tspws_hip_convergence_batch_stats(self.h, C.byref(st)), "convergence_batch_stats")
-        return dict(zip(("single_steps", "two_stage_steps", "rows", "rounds", "looped", "empty"), list(st)))
+        return self._stats("convergence_batch_stats", ("single_steps", "two_stage_steps", "rows", "rounds", "looped", "empty"))
 
     def close(self):
         if getattr(self, "h", None):
@@ -1313,11 +1204,9 @@ def jackknife_selection_batch(times, first, n, d):
     import math
     import numpy as np
     times = np.ascontiguousarray(times, dtype=np.int64)
-    f = np.asarray(first)
-    if times.ndim != 1 or f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu":
-        raise TspwsError("times must be 1-D start times and first a 1-D integer array of B + 1 ensemble offsets")
-    if (f < 0).any() or (np.diff(f) < 0).any() or int(f[-1]) > times.size:
-        raise TspwsError(f"first must be non-decreasing offsets into the {times.size} start times")
+    if times.ndim != 1:
+        raise TspwsError("times must be 1-D start times")
+    f, _, _ = _offsets(first, times.size, "start times")
     if not 0 < d < n:
         raise TspwsError(f"jackknife needs 0 < d < n, got n = {n}, d = {d}")
     Cn = math.comb(n, d)
@@ -1335,14 +1224,11 @@ def subsampling_selection_batch(first, M, prob):
     and every mask in order, ceil(M_b * prob) of the ensemble's columns of that row are 1, drawn with libc rand() in the order of a loop of
     single calls over the ensembles."""
     import numpy as np
-    f = np.asarray(first)
-    if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu" or (f < 0).any() or (np.diff(f) < 0).any():
-        raise TspwsError("first must be a 1-D array of B + 1 non-decreasing, non-negative integer offsets")
+    f, B, T = _offsets(first)
     if not 0 <= prob <= 1:
         raise TspwsError("prob must lie in [0, 1]")
-    f = np.ascontiguousarray(f, dtype=np.uint64)
-    sel = np.zeros((int(M), int(f[-1] - f[0])), np.int8)
-    if load().tspws_subsampling_plan_batch(sel.ctypes.data, f.ctypes.data, f.size - 1, int(M), float(prob)):
+    sel = np.zeros((int(M), T), np.int8)
+    if load().tspws_subsampling_plan_batch(sel.ctypes.data, f.ctypes.data, B, int(M), float(prob)):
         raise TspwsError("tspws_subsampling_plan_batch refused its arguments")
     return sel
 
@@ -1352,12 +1238,9 @@ def bootstrap_counts_batch(first, M):
     replica in order, M_b draws with replacement among the ensemble's columns of that row (its counts sum to M_b), drawn with libc rand()
     in the order of a loop over the ensembles."""
     import numpy as np
-    f = np.asarray(first)
-    if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu" or (f < 0).any() or (np.diff(f) < 0).any():
-        raise TspwsError("first must be a 1-D array of B + 1 non-decreasing, non-negative integer offsets")
-    f = np.ascontiguousarray(f, dtype=np.uint64)
-    cnt = np.zeros((int(M), int(f[-1] - f[0])), np.uint8)
-    if load().tspws_bootstrap_plan_batch(cnt.ctypes.data, f.ctypes.data, f.size - 1, int(M)):
+    f, B, T = _offsets(first)
+    cnt = np.zeros((int(M), T), np.uint8)
+    if load().tspws_bootstrap_plan_batch(cnt.ctypes.data, f.ctypes.data, B, int(M)):
         raise TspwsError("tspws_bootstrap_plan_batch refused its arguments")
     return cnt
 
@@ -1367,21 +1250,14 @@ def selection_from_scores(score, first, rule, a):
     T = first[-1] - first[0]), `rule` = "threshold" / 0 (keep iff score >= a) or "mad" / 1 (per ensemble over its finite scores: keep iff
     score >= median - a * 1.4826 * MAD).  NaN is never kept.  Returns (sel int8 [T], kept uint32 [B])."""
     import numpy as np
-    f = np.asarray(first)
-    if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu" or (f < 0).any() or (np.diff(f) < 0).any():
-        raise TspwsError("first must be a 1-D array of B + 1 non-decreasing, non-negative integer offsets")
-    f = np.ascontiguousarray(f, dtype=np.uint64)
-    if hasattr(score, "detach"):
-        score = score.detach().cpu().numpy()
-    sc = np.ascontiguousarray(score, dtype=np.float64)
-    if sc.shape != (int(f[-1] - f[0]),):
-        raise TspwsError(f"score must be one plane of {int(f[-1] - f[0])} scores, got {sc.shape}")
+    f, B, T = _offsets(first)
+    sc = _score_plane(score, T)
     r = RULES.get(rule, rule)
     if r not in (0, 1):
         raise TspwsError(f"rule must be one of {tuple(RULES)} (or 0 / 1), got {rule!r}")
-    sel = np.zeros(sc.size, np.int8)
-    kept = np.zeros(f.size - 1, np.uint32)
-    rc = load().tspws_selection_from_scores(sel.ctypes.data, kept.ctypes.data, sc.ctypes.data, f.ctypes.data, f.size - 1, int(r), float(a))
+    sel = np.zeros(T, np.int8)
+    kept = np.zeros(B, np.uint32)
+    rc = load().tspws_selection_from_scores(sel.ctypes.data, kept.ctypes.data, sc.ctypes.data, f.ctypes.data, B, int(r), float(a))
     if rc:
         raise TspwsError(f"tspws_selection_from_scores refused its arguments (code {rc})")
     return sel, kept
@@ -1450,20 +1326,13 @@ def weights_from_scores(score, first, rule, a=1.0):
     score > 0, else 0, divided by the ensemble's largest w; `a` is ignored).  NaN scores give weight 0.  Returns w float64 [T], one row of
     Plan.weighted_stack_batch's weights."""
     import numpy as np
-    f = np.asarray(first)
-    if f.ndim != 1 or f.size < 1 or f.dtype.kind not in "iu" or (f < 0).any() or (np.diff(f) < 0).any():
-        raise TspwsError("first must be a 1-D array of B + 1 non-decreasing, non-negative integer offsets")
-    f = np.ascontiguousarray(f, dtype=np.uint64)
-    if hasattr(score, "detach"):
-        score = score.detach().cpu().numpy()
-    sc = np.ascontiguousarray(score, dtype=np.float64)
-    if sc.shape != (int(f[-1] - f[0]),):
-        raise TspwsError(f"score must be one plane of {int(f[-1] - f[0])} scores, got {sc.shape}")
+    f, B, T = _offsets(first)
+    sc = _score_plane(score, T)
     r = WEIGHT_RULES.get(rule, rule)
     if r not in (0, 1):
         raise TspwsError(f"rule must be one of {tuple(WEIGHT_RULES)} (or 0 / 1), got {rule!r}")
-    w = np.zeros(sc.size, np.float64)
-    rc = load().tspws_weights_from_scores(w.ctypes.data, sc.ctypes.data, f.ctypes.data, f.size - 1, int(r), float(a))
+    w = np.zeros(T, np.float64)
+    rc = load().tspws_weights_from_scores(w.ctypes.data, sc.ctypes.data, f.ctypes.data, B, int(r), float(a))
     if rc:
         raise TspwsError(f"tspws_weights_from_scores refused its arguments (code {rc})")
     return w
