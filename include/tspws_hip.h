@@ -707,6 +707,64 @@ int  tspws_hip_stretch_rows_stats(const tspws_hip_plan *plan, tspws_hip_stretch_
  * exactly 0.  Returns 0; 1 for NULL eps; 2 for an even E, E < 3 or an eps_max outside (0, 0.5] (nothing written). */
 int  tspws_stretch_grid(double *eps, double eps_max, unsigned E);
 
+/* ---- dv/v per band from the wavelet cross-spectrum ---- */
+/* The time-frequency estimate of dv/v: the phase of the wavelet cross-spectrum between a row and its ensemble's reference becomes a delay
+ * per coefficient, and per (row, window, band of scales) the delay is regressed on the lag.  The frequency-resolved companion of
+ * tspws_hip_stretch_rows: rows, counts, references, z and windows mean what they mean there (row (b, m) takes part iff h_mtr == NULL or
+ * h_mtr[b][m] > 0; z, the zero-lag position in samples, may be fractional; 1 <= W <= 4 windows [n0, n1), n0 < n1 <= N, which may overlap).
+ * h_bands holds 1 <= R <= 64 half-open scale ranges as for tspws_hip_inverse_bands: they may overlap, cut an octave between voices, be empty.
+ * Definition.  Coefficient k < N_s of scale s sits at sample k D_s.  With c = Yc_s[k] of the row's set and r = Yr_s[k] of the reference's, in FP64:
+ *   xr = c.re r.re + c.im r.im,  xi = c.im r.re - c.re r.im   (X = c conj(r)),   a = hypot(xr, xi),   phi = atan2(xi, xr)
+ *   omega_s = w0 / scale_s   (rad per sample: 2 PI dt times the centre frequency of tspws_bands_from_frequencies)
+ *   delta = phi / omega_s,   t = (double)(k D_s) - z
+ * The coefficient takes part in (w, band) iff s lies in the band, n0_w <= k D_s < n1_w, a is finite and > 0, and -- with skip_wrapped != 0 --
+ * its filter support [k D_s - c_s, k D_s - c_s + L_s) lies inside [0, N) (c_s, L_s: tspws_hip_plan_tables), which leaves out the coefficients that
+ * mix the two trace ends through the circular correlation.  d_sums is NULL or [..][W][R][9] doubles, over the coefficients that take part:
+ *   n (as a double), A = sum a, At = sum a t, Att = sum a t^2, Ad = sum a delta, Atd = sum a t delta, Add = sum a delta^2, Xr = sum xr, Xi = sum xi
+ * d_fit is [..][W][R][6] doubles from those sums, every operation rounded on its own (no contraction):
+ *   den = A Att - At At
+ *   eps_hat = (A Atd - At Ad) / den        (the slope of the delay on the lag: dv/v)
+ *   icpt    = (Att Ad - At Atd) / den      (samples)
+ *   res     = (Add - icpt Ad) - eps_hat Atd,   rms = sqrt((res > 0 ? res : 0) / A)
+ *   err     = rms sqrt(A / den)            (the slope's standard error per effective observation)
+ *   coh     = hypot(Xr, Xi) / A            (the hypot with one correction step: the correctly rounded value in all but rare cases)
+ *   fit = eps_hat, icpt, err, rms, coh, n
+ * n < 2 or !(den > 0) gives NaN, NaN, NaN, NaN, coh, n, with coh NaN when A == 0.  A row that does not take part gives five NaN and n = -1, and
+ * NaN sums.  With the library's Y, a row cur(t) = ref(t (1 + eps)) has delta ~ eps t: eps_hat is dv/v in the sign of tspws_hip_stretch_rows.
+ * The phase is NOT unwrapped: the estimate needs |omega_s eps t| < PI inside the window; that is the caller's choice of bands and windows.
+ * Nothing is atomic and every sum has a fixed order: a repeated call is bit-identical, and the sums of (row, w, band) depend only on that
+ * row's and its reference's coefficients, z, the window, the band and skip_wrapped -- not on nrow, B, M, the other bands and windows, the
+ * rounds or any padding.  The unit of work is (row, scale inside at least one band, window, segment of 256 coefficients of the window's index
+ * range of that scale, counted from its first index); a wave takes a run of short items one after the other; a final kernel adds a band's
+ * scales in increasing s and each scale's segments in increasing order (the principle of tspws_hip_inverse_bands' combining kernel).
+ *
+ * tspws_hip_wxs_coef: on coefficient sets.  d_Yc is [nrow][ncoef] complex, d_Yr [B][ncoef] complex (tspws_hip_forward_f32's layout); h_ens[nrow]
+ * names the reference set of every row (NULL: nrow == B, row i against set i); outputs [nrow][W][R][9] / [6].  In chunks of rows whose
+ * partial sums stay within TSPWS_PART_MB.
+ * tspws_hip_wxs_rows: on rows.  d_rows is [B][M][ld] floats, d_ref [B][ldr] floats; outputs [B][M][W][R][9] / [6].  In rounds of whole ensembles
+ * whose coefficient sets ((M + 1) ncoef complex each) and partial sums stay within TSPWS_PART_MB (one ensemble alone may exceed it); a round
+ * is ONE tspws_hip_forward_f32 call on its rows (those left out are transformed too), one on its references, and one pass of the two kernels.
+ * NULL plan / inputs / h_bands / h_win / d_fit, ld < max, ldr < max, R or W outside its range, s_begin > s_end, s_end > S, a bad window (n0 >= n1,
+ * n1 > max), a NaN or infinite z, an h_ens entry >= B (or no h_ens with nrow != B) and more than 2^32 - 16 rows return TSPWS_E_ARG
+ * ("wxs_coef: ..." / "wxs_rows: ...") before any device work, outputs untouched; the checks that need no plan come first.  B == 0, M == 0 or
+ * nrow == 0 returns 0 and does nothing.  Columns max .. ld-1 / ldr-1 are never read, nothing outside the two outputs is written; one small table
+ * upload per pass into scratch slots of the unit's own.  The calls wait for `stream`: on return the outputs are complete. */
+int  tspws_hip_wxs_coef(tspws_hip_plan *plan, const double *d_Yc, const double *d_Yr, const unsigned *h_ens, size_t nrow, unsigned B, double z,
+                        const tspws_band *h_bands, unsigned R, const size_t *h_win, unsigned W, int skip_wrapped, double *d_sums, double *d_fit,
+                        void *stream);
+int  tspws_hip_wxs_rows(tspws_hip_plan *plan, const float *d_rows, size_t ld, unsigned B, unsigned M, const unsigned *h_mtr, const float *d_ref,
+                        size_t ldr, double z, const tspws_band *h_bands, unsigned R, const size_t *h_win, unsigned W, int skip_wrapped,
+                        double *d_sums, double *d_fit, void *stream);
+/* How the plan's last tspws_hip_wxs_rows / tspws_hip_wxs_coef call that did work went (all zero before the first one). */
+typedef struct {
+	unsigned rounds;   /* rounds of whole ensembles (wxs_coef: chunks of rows)       */
+	unsigned rows;     /* rows that took part                                        */
+	unsigned left_out; /* rows left out by h_mtr                                     */
+	unsigned items;    /* work items per row: (scale, window, segment)               */
+	unsigned scales;   /* scales inside at least one band                            */
+} tspws_hip_wxs_stats;
+int  tspws_hip_wxs_rows_stats(const tspws_hip_plan *plan, tspws_hip_wxs_stats *stats);
+
 /* ---- convergence curves ------------------------------------------------------------------------ */
 /* Similarity / misfit of the stack of the first i+1 traces against a reference, for i = 0..mtr-1
  * (ts_pws1f_lib.c:247-314, similarity :433-449, misfit :452-462).  d_ref_ts / d_ref_ls are [max] floats on the

@@ -22,7 +22,8 @@ on the plan's device, of a shape or of at least so many elements; ``_out`` and
 ``_refs`` are its pointer-returning forms), ``_rows_out`` (``ls_out`` /
 ``ts_out`` / ``mtr_out``, given or new), ``_sel`` (selections and masks),
 ``_coef_sets`` (``Y``), ``_strided_rows`` ([B][M][N] views of a wider base),
-``_window`` and ``_stats`` (the ``*_stats()`` dicts).
+``_strided_refs`` ([B][N] reference rows likewise), ``_window``, ``_windows``
+(the (n0, n1) table) and ``_stats`` (the ``*_stats()`` dicts).
 """
 import ctypes as C
 import os
@@ -175,6 +176,9 @@ SYMBOLS = {
     "tspws_hip_stretch_rows": (_i, [_vp, _vp, _sz, _u, _u, _vp, _vp, _sz, _d, _vp, _u, _vp, _u, _vp, _vp, _vp]),
     "tspws_hip_stretch_rows_stats": (_i, [_vp, _vp]),
     "tspws_stretch_grid": (_i, [_vp, _d, _u]),
+    "tspws_hip_wxs_coef": (_i, [_vp, _vp, _vp, _vp, _sz, _u, _d, _vp, _u, _vp, _u, _i, _vp, _vp, _vp]),
+    "tspws_hip_wxs_rows": (_i, [_vp, _vp, _sz, _u, _u, _vp, _vp, _sz, _d, _vp, _u, _vp, _u, _i, _vp, _vp, _vp]),
+    "tspws_hip_wxs_rows_stats": (_i, [_vp, _vp]),
     "tspws_hip_selective_stack_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _i, _i, _d, _u, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -409,6 +413,46 @@ class Plan:
             if B > 1 and t.stride(0) != Mn * ld:
                 raise TspwsError(f"{name} must be a [B][{mid}][N] view of one [B][{mid}][ld] base (stride(0) == {mid} * stride(1))")
         return B, Mn, ld
+
+    def _strided_refs(self, ref, B):
+        """The row stride of float32 [B][N] reference rows on the plan's device, contiguous or a [:, :N] view of one [B][ldr] base."""
+        import torch
+        if not isinstance(ref, torch.Tensor) or ref.dtype != torch.float32 or tuple(ref.shape) != (B, self.N):
+            raise TspwsError(f"ref must be a float32 [{B}][{self.N}] tensor, got {getattr(ref, 'dtype', type(ref))} {tuple(getattr(ref, 'shape', ()))}")
+        if not ref.is_cuda or (ref.device.index or 0) != self.device:
+            raise TspwsError(f"ref lives on {ref.device}, the plan on cuda:{self.device}")
+        ldr = ref.stride(0) if B > 1 else self.N
+        if B and (ref.stride(1) != 1 or ldr < self.N):
+            raise TspwsError("ref must be contiguous along the samples, its rows not overlapping")
+        return ldr
+
+    @staticmethod
+    def _windows(windows):
+        """`windows` as the C table: contiguous uint64 [W][2] of (n0, n1) pairs."""
+        import numpy as np
+        try:
+            wa = np.ascontiguousarray(np.asarray(windows, dtype=np.int64))
+        except (TypeError, ValueError):
+            raise TspwsError("windows must be a sequence of (n0, n1) pairs of non-negative integers") from None
+        if wa.ndim != 2 or wa.shape[1] != 2 or (wa < 0).any():
+            raise TspwsError("windows must be a sequence of (n0, n1) pairs of non-negative integers")
+        return np.ascontiguousarray(wa, dtype=np.uint64)  # size_t
+
+    def _wxs_out(self, lead, sums, out, device):
+        """(sums or None, fit) of a wavelet cross-spectrum call, given as `out` or new (NaN-filled): float64 tensors of at least
+        prod(lead) 9 / prod(lead) 6 values."""
+        import torch
+        n = 1
+        for k in lead:
+            n *= k
+        o_sums, o_fit = (out if sums else (None, out)) if out is not None else (None, None)
+        if out is None:
+            o_fit = torch.full((*lead, 6), float("nan"), dtype=torch.float64, device=device)
+            o_sums = torch.full((*lead, 9), float("nan"), dtype=torch.float64, device=device) if sums else None
+        self._need(o_fit, "out: fit", "float64", n * 6, "tensor of >= {} values")
+        if sums:
+            self._need(o_sums, "out: sums", "float64", n * 9, "tensor of >= {} values")
+        return o_sums, o_fit
 
     def _stats(self, what, names):
         """dict(names -> counts) of tspws_hip_<what> (len(names) unsigned counters)."""
@@ -893,13 +937,7 @@ class Plan:
         import numpy as np
         import torch
         B, Mn, ld = self._strided_rows(rows)
-        if not isinstance(ref, torch.Tensor) or ref.dtype != torch.float32 or tuple(ref.shape) != (B, self.N):
-            raise TspwsError(f"ref must be a float32 [{B}][{self.N}] tensor, got {getattr(ref, 'dtype', type(ref))} {tuple(getattr(ref, 'shape', ()))}")
-        if not ref.is_cuda or (ref.device.index or 0) != self.device:
-            raise TspwsError(f"ref lives on {ref.device}, the plan on cuda:{self.device}")
-        ldr = ref.stride(0) if B > 1 else self.N
-        if B and (ref.stride(1) != 1 or ldr < self.N):
-            raise TspwsError("ref must be contiguous along the samples, its rows not overlapping")
+        ldr = self._strided_refs(ref, B)
         try:
             ea = np.ascontiguousarray(np.asarray(eps, dtype=np.float64))
             wa = np.ascontiguousarray(np.asarray(windows, dtype=np.int64))
@@ -926,6 +964,65 @@ class Plan:
     def stretch_rows_stats(self):
         """How the last stretch_rows call with B, M > 0 went (tspws_hip_stretch_rows_stats): dict(rounds, segments, rows, left_out, chunks)."""
         return self._stats("stretch_rows_stats", ("rounds", "segments", "rows", "left_out", "chunks"))
+
+    def forward(self, rows):
+        """The forward frame transform of float32 cuda rows [ntr][N] (contiguous along the samples; a row stride through a [:, :N] view is
+        taken as it is) in ONE tspws_hip_forward_f32 call: the complex128 cuda tensor [ntr][ncoef].  The output holds NaN before the call;
+        synchronises."""
+        import torch
+        ntr, ld = self._traces(rows)
+        Y = torch.full((ntr, self.ncoef), complex(float("nan"), float("nan")), dtype=torch.complex128, device=rows.device)
+        if ntr:
+            check(self.lib.tspws_hip_forward_f32(self.h, rows.data_ptr(), ntr, ld, Y.data_ptr(), self._stream()), "forward")
+            torch.cuda.synchronize(rows.device)
+        return Y
+
+    def wxs_coef(self, Yc, Yr, z, bands, windows, ens=None, skip_wrapped=False, sums=False, out=None):
+        """dv/v per band from the wavelet cross-spectrum of coefficient sets (tspws_hip_wxs_coef): `Yc` [nrow][ncoef] against `Yr` [B][ncoef]
+        (complex128, as for inverse: what forward returns), `ens` = None (nrow == B, row i against set i) or the uint32 [nrow] reference set of
+        every row.  `z` = the zero-lag position in samples, `bands` = 1 to 64 scale ranges (s_begin, s_end), `windows` = 1 to 4 pairs (n0, n1);
+        skip_wrapped leaves out the coefficients whose filter support wraps round the trace ends.  Returns the fit, float64 cuda
+        [nrow][W][R][6] = eps_hat (dv/v), icpt, err, rms, coh, n; with sums=True the pair (sums [nrow][W][R][9], fit).  `out` as for
+        stretch_rows.  New outputs hold NaN before the call.  Synchronises."""
+        import numpy as np
+        bt = band_table(bands)
+        wa = self._windows(windows)
+        Yc, _ = self._coef_sets(Yc, "nrow")
+        Yr, _ = self._coef_sets(Yr, "B")
+        nrow, B = Yc.shape[0], Yr.shape[0]
+        ens = _host_array(ens, "ens", np.uint32, (nrow,), optional=True)
+        if ens is None and nrow != B:
+            raise TspwsError(f"without ens, Yc and Yr must hold as many sets ({nrow} and {B})")
+        R, W = bt.shape[0], wa.shape[0]
+        o_sums, o_fit = self._wxs_out((nrow, W, R), sums, out, Yc.device)
+        check(self.lib.tspws_hip_wxs_coef(self.h, Yc.data_ptr(), Yr.data_ptr(), ens.ctypes.data if ens is not None else None, nrow, B, float(z),
+                                          bt.ctypes.data, R, wa.ctypes.data, W, int(bool(skip_wrapped)), o_sums.data_ptr() if sums else None,
+                                          o_fit.data_ptr(), self._stream()), "wxs_coef")
+        return (o_sums, o_fit) if sums else o_fit
+
+    def wxs_rows(self, rows, ref, z, bands, windows, mtr=None, skip_wrapped=False, sums=False, out=None):
+        """dv/v per band from the wavelet cross-spectrum of rows (tspws_hip_wxs_rows): `rows`, `ref`, `z`, `windows` and `mtr` as for
+        stretch_rows, `bands` = 1 to 64 scale ranges (s_begin, s_end) (see bands_from_frequencies).  The rows are transformed on the device in
+        rounds of whole ensembles and never leave it.  Returns the fit, float64 cuda [B][M][W][R][6] = eps_hat (dv/v), icpt, err, rms, coh, n
+        (rows left out: NaN and n = -1); with sums=True the pair (sums [B][M][W][R][9], fit).  `out` as for stretch_rows.  New outputs hold
+        NaN before the call.  Synchronises."""
+        import numpy as np
+        B, Mn, ld = self._strided_rows(rows)
+        ldr = self._strided_refs(ref, B)
+        bt = band_table(bands)
+        wa = self._windows(windows)
+        R, W = bt.shape[0], wa.shape[0]
+        mtr = _host_array(mtr, "mtr", np.uint32, (B, Mn), optional=True)
+        o_sums, o_fit = self._wxs_out((B, Mn, W, R), sums, out, rows.device)
+        if B and Mn:  # (an empty tensor has no address)
+            check(self.lib.tspws_hip_wxs_rows(self.h, rows.data_ptr(), ld, B, Mn, mtr.ctypes.data if mtr is not None else None, ref.data_ptr(), ldr,
+                                              float(z), bt.ctypes.data, R, wa.ctypes.data, W, int(bool(skip_wrapped)),
+                                              o_sums.data_ptr() if sums else None, o_fit.data_ptr(), self._stream()), "wxs_rows")
+        return (o_sums, o_fit) if sums else o_fit
+
+    def wxs_rows_stats(self):
+        """How the last wxs_rows / wxs_coef call that did work went (tspws_hip_wxs_rows_stats): dict(rounds, rows, left_out, items, scales)."""
+        return self._stats("wxs_rows_stats", ("rounds", "rows", "left_out", "items", "scales"))
 
     def convergence(self, traces, ref_ts, ref_ls, steps=False):
         """Convergence curves of ONE ensemble (tspws_hip_convergence) on device tensors: `traces` float32 [mtr][N], `ref_ts` / `ref_ls`
