@@ -765,6 +765,69 @@ typedef struct {
 } tspws_hip_wxs_stats;
 int  tspws_hip_wxs_rows_stats(const tspws_hip_plan *plan, tspws_hip_wxs_stats *stats);
 
+/* ---- dv/v by the moving-window cross-spectrum (MWCS; Clarke et al. 2011) -------------------------------------------------
+ * Rows, counts, references, z and the lag ranges as for tspws_hip_stretch_rows: d_rows is [B][M][ld] floats, h_mtr NULL or [B][M] (row (b, m)
+ * takes part iff h_mtr == NULL or the count is > 0), d_ref [B][ldr] floats, z may be fractional or outside [0, max), h_win holds 1 <= W <= 4
+ * pairs [n0_w, n1_w), n0 < n1 <= max, which may overlap.
+ * Parameters: L = window length in samples, 16 <= L <= 1024 (any L, no multiple of 4 needed); 1 <= hop <= L; P = DFT length, a power of two,
+ * L <= P <= 4096; [q0, q1) = the band as DFT bins, 1 <= q0, q0 + 2 <= q1 <= P/2 (tspws_mwcs_bins makes them from frequencies); h = smoothing
+ * half-width in bins, 0 <= h <= 8; taper = the fraction of the window under the cosine taper, in [0, 1]; min_coh, max_err, max_delta = the
+ * filters of stage 3 (max_err, max_delta may be +inf); err_floor > 0.  The extended bin range is [qa, qb) = [max(0, q0 - h),
+ * min(P/2 + 1, q1 + h)), Qx = qb - qa <= 64.
+ * WINDOWS.  Range w holds J_w = (n1_w - n0_w >= L) ? (n1_w - n0_w - L) / hop + 1 : 0 windows starting at n_j = n0_w + j hop; J = sum J_w,
+ * 1 <= J <= 4096; the windows are numbered range after range; t_j = ((double)n_j + 0.5 (L - 1)) - z.
+ * STAGE 1, spectra.  tspws_mwcs_basis writes the table the device uses (tspws_mwcs_basis_size doubles: g[L] | C[L][Qx] | S[L][Qx] | Tc[Qx] |
+ * Ts[Qx] | k[2 h + 1] | v[Qx]): g = the cosine taper -- with a = taper L / 2 and x = min(l + 1/2, L - 1/2 - l), g[l] = 0.5 (1 - cos(PI x / a))
+ * for x < a, else 1 --, C[l][q] = g[l] cos(2 PI ((q l) mod P) / P), S[l][q] = -g[l] sin(same) for q in [qa, qb), every entry rounded to
+ * double once; Tc[q] = sum_l C[l][q], Ts likewise, added in ascending l; k[d + h] = 0.5 (1 + cos(PI d / (h + 1))); v[q] = 2 PI q / P.  The
+ * device never evaluates a sine.  For a window x[l] = (double)row[n_j + l], in FP64: mu = (sum_l x[l]) / L and
+ * F[q] = (sum_l x[l] C[l][q] - mu Tc[q]) + i (sum_l x[l] S[l][q] - mu Ts[q]), the demeaned, tapered window's DFT bin q of length P; the sums
+ * over l in any order (the matrix pipe).  The reference's windows go through the same code as one more row of their ensemble.
+ * STAGE 2, per (row, window); from here every FP64 operation is rounded on its own, in the stated order.  With c = F of the row, r = F of
+ * the reference, per bin of [qa, qb): Xr = c.re r.re + c.im r.im, Xi = c.im r.re - c.re r.im, Pc = c.re c.re + c.im c.im, Pr likewise.
+ * For q in [q0, q1) and each of the four planes sm(v)[q] = (sum_{d = -h..h, qa <= q + d < qb} k[d] v[q + d]) / (sum of the same k[d]),
+ * both sums from 0 in ascending d.  a = hypot(smXr, smXi), coh = a / sqrt(smPc smPr), phi = atan2(smXi, smXr) (not unwrapped:
+ * |v delta| < PI is the caller's choice of band and ranges), cc = min(coh, 0.99), wq = sqrt(cc cc / (1 - cc cc) * sqrt(a)).  In ascending
+ * q: Svv = sum (wq v) v, Svp = sum (wq v) phi; delta = Svp / Svv, in samples; s2 = (sum (phi - delta v)^2) / (nq - 1), nq = q1 - q0;
+ * err = sqrt((sum (wq v)(wq v)) s2) / Svv; mcoh = (sum coh) / nq.  A row cur(t) = ref(t (1 + eps)) has delta ~ eps t.  A bin with
+ * smPc smPr == 0 gives the window delta = err = mcoh = NaN.  d_win is NULL or [B][M][J][3] = delta, err, mcoh.
+ * STAGE 3, per (row, range).  Window j takes part iff delta and err are finite, err <= max_err, mcoh >= min_coh and |delta| <= max_delta.
+ * p = 1 / (e e), e = max(err, err_floor); in ascending j: S = sum p, St = sum (p t), Stt = sum (p t) t, Sd = sum p delta,
+ * Std = sum (p t) delta; den = S Stt - St St; eps_hat = (S Std - St Sd) / den, icpt = (Stt Sd - St Std) / den, err_eps = sqrt(S / den);
+ * eps0 = Std / Stt and err0 = sqrt(1 / Stt), the fit through the origin.  d_fit is [B][M][W][6] = eps_hat, icpt, err_eps, eps0, err0, n.
+ * n < 2 or !(den > 0) gives NaN for the first three; the through-origin pair stands when n >= 1 and Stt > 0 (else NaN).  A row that does not
+ * take part gives five NaN and n = -1, and NaN in d_win and d_spec.  eps_hat is dv/v in the sign of stretch_rows and wxs_rows.
+ * d_spec (NULL or [B][M][J][Qx] complex) and d_spec_ref (NULL or [B][J][Qx] complex) return stage 1.
+ * Nothing is atomic, every output has one writer: a repeated call is bit-identical, and the values of (b, m, j) depend on that row, its
+ * reference, the window and the parameters alone -- not on B, M, the other ranges, the rounds (whole ensembles whose spectra and window
+ * results stay within TSPWS_PART_MB; one ensemble alone may exceed it) or a tile's padding.
+ * NULL plan / rows / ref / par / h_win / d_fit, ld < max, ldr < max, a parameter outside its range, Qx > 64, J > 4096, J == 0, a bad range
+ * (n0 >= n1, n1 > max), a NaN or infinite z and more than 2^32 - 16 rows return TSPWS_E_ARG ("mwcs_rows: ...") before any device work, outputs
+ * untouched; the checks that need no plan come first.  B == 0 or M == 0 returns 0 and does nothing.  Columns max .. ld-1 / ldr-1 are never
+ * read, nothing outside the outputs is written; one table upload per round into scratch slots of the unit's own.  The call waits for
+ * `stream`: on return the outputs are complete. */
+typedef struct {
+	unsigned L, hop, P, q0, q1, h;
+	double taper, min_coh, max_err, max_delta, err_floor;
+} tspws_mwcs_par;
+/* The bins with f_lo <= q / (P dt) < f_hi, without bin 0 and below P/2: q0 = max(1, ceil(f_lo P dt)), q1 = min(P/2, ceil(f_hi P dt)).
+ * Returns 0; 1: NULL; 2: P no power of two in [16, 4096], dt <= 0, f_lo < 0 or f_hi <= f_lo; 3: fewer than two bins. */
+int    tspws_mwcs_bins(unsigned P, double dt, double f_lo, double f_hi, unsigned *q0, unsigned *q1);
+size_t tspws_mwcs_basis_size(const tspws_mwcs_par *par);          /* doubles of the table; 0 for parameters the call would refuse */
+int    tspws_mwcs_basis(const tspws_mwcs_par *par, double *tab);  /* 0; 1: NULL; 2: parameters the call would refuse */
+int  tspws_hip_mwcs_rows(tspws_hip_plan *plan, const float *d_rows, size_t ld, unsigned B, unsigned M, const unsigned *h_mtr, const float *d_ref,
+                         size_t ldr, double z, const tspws_mwcs_par *par, const size_t *h_win, unsigned W, double *d_win, double *d_fit,
+                         double *d_spec, double *d_spec_ref, void *stream);
+/* How the plan's last tspws_hip_mwcs_rows call with B, M > 0 went (all zero before the first one). */
+typedef struct {
+	unsigned rounds;   /* rounds of whole ensembles                                  */
+	unsigned rows;     /* rows that took part                                        */
+	unsigned left_out; /* rows left out by h_mtr                                     */
+	unsigned windows;  /* J: windows of all lag ranges                               */
+	unsigned bins;     /* Qx: bins of the band with the smoothing margins            */
+} tspws_hip_mwcs_stats;
+int  tspws_hip_mwcs_rows_stats(const tspws_hip_plan *plan, tspws_hip_mwcs_stats *stats);
+
 /* ---- convergence curves ------------------------------------------------------------------------ */
 /* Similarity / misfit of the stack of the first i+1 traces against a reference, for i = 0..mtr-1
  * (ts_pws1f_lib.c:247-314, similarity :433-449, misfit :452-462).  d_ref_ts / d_ref_ls are [max] floats on the

@@ -179,6 +179,11 @@ SYMBOLS = {
     "tspws_hip_wxs_coef": (_i, [_vp, _vp, _vp, _vp, _sz, _u, _d, _vp, _u, _vp, _u, _i, _vp, _vp, _vp]),
     "tspws_hip_wxs_rows": (_i, [_vp, _vp, _sz, _u, _u, _vp, _vp, _sz, _d, _vp, _u, _vp, _u, _i, _vp, _vp, _vp]),
     "tspws_hip_wxs_rows_stats": (_i, [_vp, _vp]),
+    "tspws_hip_mwcs_rows": (_i, [_vp, _vp, _sz, _u, _u, _vp, _vp, _sz, _d, _vp, _vp, _u, _vp, _vp, _vp, _vp, _vp]),
+    "tspws_hip_mwcs_rows_stats": (_i, [_vp, _vp]),
+    "tspws_mwcs_bins": (_i, [_u, _d, _d, _d, _vp, _vp]),
+    "tspws_mwcs_basis_size": (_sz, [_vp]),
+    "tspws_mwcs_basis": (_i, [_vp, _vp]),
     "tspws_hip_selective_stack_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _i, _i, _d, _u, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_convergence_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1024,6 +1029,38 @@ class Plan:
         """How the last wxs_rows / wxs_coef call that did work went (tspws_hip_wxs_rows_stats): dict(rounds, rows, left_out, items, scales)."""
         return self._stats("wxs_rows_stats", ("rounds", "rows", "left_out", "items", "scales"))
 
+    def mwcs_rows(self, rows, ref, z, par, windows, mtr=None, win=False, spec=False):
+        """dv/v by the moving-window cross-spectrum (tspws_hip_mwcs_rows): `rows`, `ref`, `z`, `windows` (the lag ranges) and `mtr` as for
+        stretch_rows, `par` = the parameters (mwcs_par, or a dict of its arguments).  Returns the fit, float64 cuda [B][M][W][6] = eps_hat
+        (dv/v), icpt, err_eps, eps0, err0, n (rows left out: NaN and n = -1).  With win=True and / or spec=True a dict: fit, win
+        ([B][M][J][3] = delta, err, mcoh per window), spec ([B][M][J][Qx] complex128) and spec_ref ([B][J][Qx]).  New outputs hold NaN
+        before the call.  Synchronises."""
+        import numpy as np
+        import torch
+        B, Mn, ld = self._strided_rows(rows)
+        ldr = self._strided_refs(ref, B)
+        par = par if isinstance(par, MwcsPar) else mwcs_par(**par)
+        wa = self._windows(windows)
+        W = wa.shape[0]
+        mtr = _host_array(mtr, "mtr", np.uint32, (B, Mn), optional=True)
+        J, Qx = mwcs_windows(par, wa).shape[0], mwcs_qrange(par)[2]
+        nan = float("nan")
+        o_fit = torch.full((B, Mn, W, 6), nan, dtype=torch.float64, device=rows.device)
+        o_win = torch.full((B, Mn, J, 3), nan, dtype=torch.float64, device=rows.device) if win else None
+        o_spec = torch.full((B, Mn, J, Qx), complex(nan, nan), dtype=torch.complex128, device=rows.device) if spec else None
+        o_sref = torch.full((B, J, Qx), complex(nan, nan), dtype=torch.complex128, device=rows.device) if spec else None
+        if B and Mn:  # (an empty tensor has no address)
+            check(self.lib.tspws_hip_mwcs_rows(self.h, rows.data_ptr(), ld, B, Mn, mtr.ctypes.data if mtr is not None else None, ref.data_ptr(), ldr,
+                                               float(z), C.addressof(par), wa.ctypes.data, W, o_win.data_ptr() if win else None, o_fit.data_ptr(),
+                                               o_spec.data_ptr() if spec else None, o_sref.data_ptr() if spec else None, self._stream()), "mwcs_rows")
+        if not win and not spec:
+            return o_fit
+        return dict(fit=o_fit, win=o_win, spec=o_spec, spec_ref=o_sref)
+
+    def mwcs_rows_stats(self):
+        """How the last mwcs_rows call with B, M > 0 went (tspws_hip_mwcs_rows_stats): dict(rounds, rows, left_out, windows, bins)."""
+        return self._stats("mwcs_rows_stats", ("rounds", "rows", "left_out", "windows", "bins"))
+
     def convergence(self, traces, ref_ts, ref_ls, steps=False):
         """Convergence curves of ONE ensemble (tspws_hip_convergence) on device tensors: `traces` float32 [mtr][N], `ref_ts` / `ref_ls`
         float32 [N] references of the ts-PWS / linear curve.  Returns (ts_sim, ts_misfit, ls_sim, ls_misfit) as float64 numpy [mtr]; with
@@ -1369,6 +1406,63 @@ def stretch_grid(eps_max, E):
     if rc:
         raise TspwsError(f"tspws_stretch_grid refused its arguments (code {rc}): E odd and >= 3, 0 < eps_max <= 0.5")
     return eps
+
+
+class MwcsPar(C.Structure):
+    """tspws_mwcs_par"""
+    _fields_ = [("L", C.c_uint), ("hop", C.c_uint), ("P", C.c_uint), ("q0", C.c_uint), ("q1", C.c_uint), ("h", C.c_uint), ("taper", C.c_double),
+                ("min_coh", C.c_double), ("max_err", C.c_double), ("max_delta", C.c_double), ("err_floor", C.c_double)]
+
+
+def mwcs_par(L, hop, P, q0, q1, h=0, taper=0.0, min_coh=0.0, max_err=float("inf"), max_delta=float("inf"), err_floor=1e-6):
+    """The parameters of Plan.mwcs_rows (tspws_mwcs_par): window length, hop and DFT length in samples, the band [q0, q1) in DFT bins (see
+    mwcs_bins), the smoothing half-width in bins, the taper fraction and the filters of the regression on the lag.  The library judges them."""
+    try:
+        return MwcsPar(int(L), int(hop), int(P), int(q0), int(q1), int(h), float(taper), float(min_coh), float(max_err), float(max_delta), float(err_floor))
+    except (TypeError, ValueError, OverflowError):
+        raise TspwsError("mwcs_par: L, hop, P, q0, q1, h must be non-negative integers below 2^32, the rest floats") from None
+
+
+def mwcs_bins(P, dt, f_lo, f_hi):
+    """(q0, q1) of tspws_mwcs_bins: the DFT bins of length P with f_lo <= q / (P dt) < f_hi, without bin 0 and below P / 2."""
+    q0, q1 = C.c_uint(0), C.c_uint(0)
+    rc = load().tspws_mwcs_bins(int(P), float(dt), float(f_lo), float(f_hi), C.byref(q0), C.byref(q1)) if 0 <= int(P) < 2 ** 32 else 2
+    if rc:
+        raise TspwsError(f"tspws_mwcs_bins refused its arguments (code {rc}): P a power of two in [16, 4096], dt > 0, 0 <= f_lo < f_hi, two bins or more")
+    return q0.value, q1.value
+
+
+def mwcs_qrange(par):
+    """(qa, qb, Qx) of the parameters: the band with its smoothing margins, [max(0, q0 - h), min(P / 2 + 1, q1 + h))."""
+    qa, qb = max(0, par.q0 - par.h), min(par.P // 2 + 1, par.q1 + par.h)
+    return qa, qb, qb - qa
+
+
+def mwcs_windows(par, windows):
+    """The windows of the lag ranges, int64 [J][2] = (first sample, range): range w = (n0, n1) holds the windows n0 + j hop while they end
+    at or before n1, numbered range after range."""
+    import numpy as np
+    out = [(n, w) for w, (n0, n1) in enumerate(np.asarray(windows, dtype=np.int64).reshape(-1, 2).tolist())
+           for n in range(n0, n1 - par.L + 1, max(par.hop, 1))]
+    return np.array(out, dtype=np.int64).reshape(-1, 2)
+
+
+def mwcs_basis(par):
+    """The table of tspws_mwcs_basis as a dict of float64 arrays: g [L], C and S [L][Qx], Tc and Ts [Qx], k [2 h + 1], v [Qx]."""
+    import numpy as np
+    par = par if isinstance(par, MwcsPar) else mwcs_par(**par)
+    lib = load()
+    n = lib.tspws_mwcs_basis_size(C.addressof(par))
+    if not n:
+        raise TspwsError("tspws_mwcs_basis refused the parameters")
+    tab = np.empty(n, np.float64)
+    rc = lib.tspws_mwcs_basis(C.addressof(par), tab.ctypes.data)
+    if rc:
+        raise TspwsError(f"tspws_mwcs_basis refused the parameters (code {rc})")
+    L, Qx, nk = par.L, mwcs_qrange(par)[2], 2 * par.h + 1
+    cuts = np.cumsum([0, L, L * Qx, L * Qx, Qx, Qx, nk, Qx])
+    parts = [tab[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+    return dict(g=parts[0], C=parts[1].reshape(L, Qx), S=parts[2].reshape(L, Qx), Tc=parts[3], Ts=parts[4], k=parts[5], v=parts[6])
 
 
 def band_table(bands):
