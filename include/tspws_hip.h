@@ -828,6 +828,59 @@ typedef struct {
 } tspws_hip_mwcs_stats;
 int  tspws_hip_mwcs_rows_stats(const tspws_hip_plan *plan, tspws_hip_mwcs_stats *stats);
 
+/* ---- dv/v by dynamic time warping (DTW; Hale 2013, Mikesell et al. 2015) --------------------------------------------------
+ * The delay as a function of lag: per (row, lag range) the integer lag path that aligns the row with its ensemble's reference at the smallest
+ * accumulated squared error, and the regression of that path on the lag.  Unlike the cross-spectral estimates it survives a cycle skip, and
+ * it returns delta(t) itself.  Rows, counts, references, z and the lag ranges as for tspws_hip_stretch_rows: d_rows is [B][M][ld] floats, h_mtr
+ * NULL or [B][M] (row (b, m) takes part iff h_mtr == NULL or the count is > 0), d_ref [B][ldr] floats, z may be fractional or outside
+ * [0, max), h_win holds 1 <= W <= 4 pairs [n0_w, n1_w), n0 < n1 <= max, which may overlap.
+ * Parameters: 1 <= Lmax <= 127, the largest lag: nl = 2 Lmax + 1 lags l = -Lmax .. Lmax; 1 <= b <= 8, the strain limit: the lag changes by at
+ * most one sample per b samples.  n_w = n1_w - n0_w <= 131072 for every range (the integer sums below are then exact in a double);
+ * T = sum_w n_w.
+ * DEFINITION.  Every FP64 operation is rounded on its own, in the stated order, with no contraction anywhere.  For row c, reference r,
+ * range w, N = max, i = 0 .. n_w - 1, n = n0_w + i:
+ * 1. Normalisation.  mc = max_i |c[n]|; mr = max |r[k]| over k in [max(0, n0_w - Lmax), min(N, n1_w + Lmax)); both in float, hence exact.
+ *    ac = 1.0 / (double)mc, ar = 1.0 / (double)mr.  mc == 0, mr == 0, a non-finite mc or mr, or a NaN among those samples makes the
+ *    (row, range) DEAD.
+ * 2. Error.  e[i][l] = d d, d = (double)c[n] ac - (double)r[clamp(n + l, 0, N - 1)] ar: both products rounded before the subtraction; a lag
+ *    that points outside the trace takes the nearest sample inside.
+ * 3. Accumulation, ascending i.  D[0][l] = e[0][l].  For i >= 1, ib = max(0, i - b): dc = D[i-1][l]; for l > -Lmax, dm = D[ib][l-1], then
+ *    dm = dm + e[k][l-1] for k = i-1 down to ib+1, else dm = +inf; dp likewise with l+1 (+inf at l = Lmax).  The choice is C if dc <= dm &&
+ *    dc <= dp, else Mn if dm <= dp, else Pl; D[i][l] = e[i][l] + (the chosen one of dc, dm, dp).
+ * 4. Backtracking.  l* = the first l in ascending order with the smallest D[n_w-1][l]; lag[n_w-1] = l*.  At (i, l): choice C gives
+ *    lag[i-1] = l, continue at (i-1, l); Mn gives lag[k] = l-1 for k = i-1 .. ib, continue at (ib, l-1); Pl the same with l+1.  Stop at i = 0.
+ * 5. Fit.  As 64-bit integers, then converted to double (all exact): S = n_w, Si = sum i, Sii = sum i^2, Sl = sum lag[i], Sil = sum i lag[i],
+ *    Sll = sum lag[i]^2, clip = the number of i with |lag[i]| == Lmax.  Then
+ *      den = S Sii - Si Si,   num = S Sil - Si Sl,   eps_hat = num / den,   t0 = ((double)n0_w - z) + Si / S,   icpt = Sl / S - eps_hat t0
+ *      res = (Sll - (Sl / S) Sl) - eps_hat (num / S),   rms = sqrt((res > 0 ? res : 0) / S),   err = rms sqrt(S / den)
+ *      dist = D[n_w-1][l*] / S
+ * d_fit is [B][M][W][6] doubles = eps_hat, icpt, err, rms, dist, clip (n_w is the caller's own n1_w - n0_w and is not returned).  icpt is the lag
+ * at z, in samples; eps_hat the slope of the lag on n - z: a row cur(t) = ref(t (1 + eps)) has its best match at lag ~ eps t, so eps_hat is dv/v
+ * in the sign of stretch_rows, wxs_rows and mwcs_rows.  n_w == 1 (den == 0) gives NaN for eps_hat, icpt and err; rms (0), dist and clip stand.
+ * A dead (row, range) and a row that does not take part give five NaN and clip = -1, and lags INT_MIN.
+ * d_lag is NULL or [B][M][T] ints: the path of range w at [off_w, off_w + n_w), off_w = sum of the n of the ranges before it.
+ * Nothing is atomic, every output has one writer: a repeated call is bit-identical, and the values of (b, m, w) depend on that row, its
+ * reference, z, the range and par alone -- not on B, M, the other ranges, the rounds or any padding.  One wave takes a (row, range): the
+ * lags on the lanes (1, 2 or 4 consecutive lags each), two bits of choice per (sample, lag) in the wave's plane of ceil(n_w / 16) x 64 ceil(nl / 64)
+ * 32-bit words in plan scratch, the same wave backtracks.  The call runs in rounds of whole ensembles whose planes stay within TSPWS_PART_MB
+ * (one ensemble alone may exceed it), one table upload per round into scratch slots of the unit's own.
+ * NULL plan / rows / ref / par / h_win / d_fit, ld < max, ldr < max, Lmax, b or W outside its range, a bad range (n0 >= n1, n1 > max, longer
+ * than 131072), a NaN or infinite z and more than 2^32 - 16 rows return TSPWS_E_ARG ("dtw_rows: ...") before any device work, outputs
+ * untouched; the checks that need no plan come first.  B == 0 or M == 0 returns 0 and does nothing.  Columns max .. ld-1 / ldr-1 are never
+ * read, nothing outside the outputs is written.  The call waits for `stream`: on return the outputs are complete. */
+typedef struct { unsigned Lmax, b; } tspws_dtw_par;
+int  tspws_hip_dtw_rows(tspws_hip_plan *plan, const float *d_rows, size_t ld, unsigned B, unsigned M, const unsigned *h_mtr, const float *d_ref,
+                        size_t ldr, double z, const tspws_dtw_par *par, const size_t *h_win, unsigned W, int *d_lag, double *d_fit, void *stream);
+/* How the plan's last tspws_hip_dtw_rows call with B, M > 0 went (all zero before the first one). */
+typedef struct {
+	unsigned rounds;   /* rounds of whole ensembles                                  */
+	unsigned rows;     /* rows that took part                                        */
+	unsigned left_out; /* rows left out by h_mtr                                     */
+	unsigned lags;     /* nl = 2 Lmax + 1                                            */
+	unsigned samples;  /* T: samples of all lag ranges                               */
+} tspws_hip_dtw_stats;
+int  tspws_hip_dtw_rows_stats(const tspws_hip_plan *plan, tspws_hip_dtw_stats *stats);
+
 /* ---- convergence curves ------------------------------------------------------------------------ */
 /* Similarity / misfit of the stack of the first i+1 traces against a reference, for i = 0..mtr-1
  * (ts_pws1f_lib.c:247-314, similarity :433-449, misfit :452-462).  d_ref_ts / d_ref_ls are [max] floats on the

@@ -182,6 +182,8 @@ SYMBOLS = {
     "tspws_hip_mwcs_rows": (_i, [_vp, _vp, _sz, _u, _u, _vp, _vp, _sz, _d, _vp, _vp, _u, _vp, _vp, _vp, _vp, _vp]),
     "tspws_hip_mwcs_rows_stats": (_i, [_vp, _vp]),
     "tspws_mwcs_bins": (_i, [_u, _d, _d, _d, _vp, _vp]),
+    "tspws_hip_dtw_rows": (_i, [_vp, _vp, _sz, _u, _u, _vp, _vp, _sz, _d, _vp, _vp, _u, _vp, _vp, _vp]),
+    "tspws_hip_dtw_rows_stats": (_i, [_vp, _vp]),
     "tspws_mwcs_basis_size": (_sz, [_vp]),
     "tspws_mwcs_basis": (_i, [_vp, _vp]),
     "tspws_hip_selective_stack_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _i, _i, _d, _u, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1061,6 +1063,33 @@ class Plan:
         """How the last mwcs_rows call with B, M > 0 went (tspws_hip_mwcs_rows_stats): dict(rounds, rows, left_out, windows, bins)."""
         return self._stats("mwcs_rows_stats", ("rounds", "rows", "left_out", "windows", "bins"))
 
+    def dtw_rows(self, rows, ref, z, par, ranges, mtr=None, lag=True):
+        """dv/v by dynamic time warping (tspws_hip_dtw_rows): `rows`, `ref`, `z`, `ranges` (the lag ranges) and `mtr` as for stretch_rows,
+        `par` = the parameters (dtw_par, or a dict of its arguments).  Returns a dict: fit, float64 cuda [B][M][W][6] = eps_hat (dv/v), icpt,
+        err, rms, dist, clip (rows left out and dead (row, range)s: NaN and clip = -1), and lag, int32 cuda [B][M][T], the integer lag path
+        of every range, range after range (INT_MIN where the fit is NaN); with lag=False only the fit.  New outputs hold NaN / INT_MIN
+        before the call.  Synchronises."""
+        import numpy as np
+        import torch
+        B, Mn, ld = self._strided_rows(rows)
+        ldr = self._strided_refs(ref, B)
+        par = par if isinstance(par, DtwPar) else dtw_par(**par)
+        wa = self._windows(ranges)
+        W = wa.shape[0]
+        T = int((wa[:, 1].astype(np.int64) - wa[:, 0].astype(np.int64)).clip(0, 1 << 20).sum())  # (the library judges the ranges)
+        mtr = _host_array(mtr, "mtr", np.uint32, (B, Mn), optional=True)
+        o_fit = torch.full((B, Mn, W, 6), float("nan"), dtype=torch.float64, device=rows.device)
+        o_lag = torch.full((B, Mn, T), -2 ** 31, dtype=torch.int32, device=rows.device) if lag else None
+        if B and Mn:  # (an empty tensor has no address)
+            check(self.lib.tspws_hip_dtw_rows(self.h, rows.data_ptr(), ld, B, Mn, mtr.ctypes.data if mtr is not None else None, ref.data_ptr(), ldr,
+                                              float(z), C.addressof(par), wa.ctypes.data, W, o_lag.data_ptr() if lag else None, o_fit.data_ptr(),
+                                              self._stream()), "dtw_rows")
+        return dict(fit=o_fit, lag=o_lag) if lag else o_fit
+
+    def dtw_rows_stats(self):
+        """How the last dtw_rows call with B, M > 0 went (tspws_hip_dtw_rows_stats): dict(rounds, rows, left_out, lags, samples)."""
+        return self._stats("dtw_rows_stats", ("rounds", "rows", "left_out", "lags", "samples"))
+
     def convergence(self, traces, ref_ts, ref_ls, steps=False):
         """Convergence curves of ONE ensemble (tspws_hip_convergence) on device tensors: `traces` float32 [mtr][N], `ref_ts` / `ref_ls`
         float32 [N] references of the ts-PWS / linear curve.  Returns (ts_sim, ts_misfit, ls_sim, ls_misfit) as float64 numpy [mtr]; with
@@ -1463,6 +1492,20 @@ def mwcs_basis(par):
     cuts = np.cumsum([0, L, L * Qx, L * Qx, Qx, Qx, nk, Qx])
     parts = [tab[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
     return dict(g=parts[0], C=parts[1].reshape(L, Qx), S=parts[2].reshape(L, Qx), Tc=parts[3], Ts=parts[4], k=parts[5], v=parts[6])
+
+
+class DtwPar(C.Structure):
+    """tspws_dtw_par"""
+    _fields_ = [("Lmax", C.c_uint), ("b", C.c_uint)]
+
+
+def dtw_par(Lmax, b=1):
+    """The parameters of Plan.dtw_rows (tspws_dtw_par): the largest lag in samples (1 .. 127) and the strain limit (1 .. 8: the lag changes by
+    at most one sample per b samples).  The library judges them."""
+    try:
+        return DtwPar(int(Lmax), int(b))
+    except (TypeError, ValueError, OverflowError):
+        raise TspwsError("dtw_par: Lmax and b must be non-negative integers below 2^32") from None
 
 
 def band_table(bands):
