@@ -881,6 +881,72 @@ typedef struct {
 } tspws_hip_dtw_stats;
 int  tspws_hip_dtw_rows_stats(const tspws_hip_plan *plan, tspws_hip_dtw_stats *stats);
 
+/* ---- group arrivals per scale (frequency-time analysis) ---- */
+/* The dispersion measurement on the rows the batched calls leave: the complex Morlet frame is a bank of narrow-band filters, and per (row,
+ * window, scale) the peaks of the envelope inside a velocity window are the group arrivals of that period (tspws_ftan_periods), with the
+ * coefficient at the peak (its phase and the phase velocity are the caller's: the device evaluates no atan2) and a noise level.  Rows, counts
+ * and z as for tspws_hip_wxs_rows: [B][M][ld] floats, row (b, m) takes part iff h_mtr == NULL or h_mtr[b][m] > 0; z, the zero-lag position in
+ * samples, may be fractional.  Scales [s_begin, s_end), s_begin < s_end <= S; Sx = s_end - s_begin.  h_win is [B][W][2]: 1 <= W <= 4 windows
+ * [n0, n1), n0 < n1 <= N, PER ENSEMBLE (station pairs differ in distance; tspws_ftan_windows makes them), which may overlap.  h_noise is NULL
+ * or [B][2]: a range [q0, q1), q0 < q1 <= N, per ensemble.  1 <= P <= 4 peaks are reported.
+ * Definition.  Coefficient k < N_s of scale s sits at sample k D_s.  Every FP64 operation is rounded on its own (no contraction).  With
+ * c = Y_s[k]:
+ *   a2[k] = c.re c.re + c.im c.im
+ * k is a member of window w iff n0 <= k D_s < n1 and -- with skip_wrapped != 0 -- its filter support [k D_s - c_s, k D_s - c_s + L_s) lies
+ * inside [0, N) (the rule of tspws_hip_wxs_rows).  A member k is a peak iff 1 <= k <= N_s - 2, a2[k-1], a2[k] and a2[k+1] are all finite,
+ * a2[k] > a2[k-1] and a2[k] >= a2[k+1].  The neighbours are indices of the scale, not members of the window: a peak at the window's first or
+ * last member is a peak, the two ends of the scale never are, and on a plateau the left sample is the peak.  The peaks of (row, w, s) are
+ * ordered by decreasing a2, ties by increasing k, and the first P are reported.  Per reported peak, with am = a2[k-1], a0 = a2[k],
+ * ap = a2[k+1]:
+ *   den = (am - 2.0 a0) + ap,   d = den != 0 ? 0.5 (am - ap) / den : 0   (the vertex of the parabola through the three, in indices)
+ *   tg = ((double)k + d) (double)D_s - z   (the group arrival as a lag in samples),   amp = sqrt(a0)
+ * d_peaks is [..][W][Sx][P][5] doubles: tg, amp, c.re, c.im, (double)k; c.re and c.im are exact copies.  The slots beyond the number of
+ * peaks hold four NaN and k = -1, and so do the rows left out.  d_noise is NULL or [..][Sx][2] doubles and must be NULL when h_noise is
+ * NULL: Q = the sum of the finite a2[k] whose k D_s lies in the ensemble's [q0, q1) (under the wrap rule when it is set) and their number as
+ * a double; a row left out gives NaN and -1.  With d_noise == NULL h_noise is checked and not used.
+ * Nothing is atomic and every output has one writer: a repeated call is bit-identical, and the values of (row, w, s) depend only on that
+ * row's coefficients of scale s, the window, z and skip_wrapped -- not on B, M, nrow, the other windows, scales or ensembles, P, the rounds
+ * or any padding; the P = 2 list is the head of the P = 4 list.  Ensembles whose windows (and noise ranges, when used) are equal by value
+ * form a class; the unit of work is (row, scale, window or noise range, segment of 256 members counted from the range's first member) and a
+ * wave takes a run of short items; a final kernel merges the segments' lists in segment order and adds the noise partials in that order.
+ *
+ * tspws_hip_ftan_coef: on coefficient sets.  d_Y is [nrow][ncoef] complex (tspws_hip_forward_f32's layout); h_ens[nrow] names the ensemble of
+ * every row (NULL: nrow == B, row i of ensemble i); outputs [nrow][W][Sx][P][5] / [nrow][Sx][2].  In chunks of rows whose partial results
+ * stay within TSPWS_PART_MB.
+ * tspws_hip_ftan_rows: on rows.  Outputs [B][M][W][Sx][P][5] / [B][M][Sx][2].  In rounds of whole ensembles whose coefficient sets (M ncoef
+ * complex each) and partial results stay within TSPWS_PART_MB (one ensemble alone may exceed it); a round is ONE tspws_hip_forward_f32 call
+ * on its rows (those left out are transformed too) and one pass of the two kernels.
+ * NULL plan / inputs / h_win / d_peaks, ld < max, W or P outside 1 .. 4, s_begin >= s_end, s_end > S, a bad window or noise range
+ * (n0 >= n1, n1 > max), d_noise without h_noise, a NaN or infinite z, an h_ens entry >= B (or no h_ens with nrow != B) and more than
+ * 2^32 - 16 rows return TSPWS_E_ARG ("ftan_coef: ..." / "ftan_rows: ...") before any device work, outputs untouched; the checks that need no
+ * plan come first.  B == 0, M == 0 or nrow == 0 returns 0 and does nothing.  Columns max .. ld-1 are never read, nothing outside the two
+ * outputs is written; one small table upload per pass into scratch slots of the unit's own.  The calls wait for `stream`: on return the
+ * outputs are complete. */
+int  tspws_hip_ftan_coef(tspws_hip_plan *plan, const double *d_Y, const unsigned *h_ens, size_t nrow, unsigned B, double z, unsigned s_begin,
+                         unsigned s_end, const size_t *h_win, unsigned W, const size_t *h_noise, unsigned P, int skip_wrapped, double *d_peaks,
+                         double *d_noise, void *stream);
+int  tspws_hip_ftan_rows(tspws_hip_plan *plan, const float *d_rows, size_t ld, unsigned B, unsigned M, const unsigned *h_mtr, double z,
+                         unsigned s_begin, unsigned s_end, const size_t *h_win, unsigned W, const size_t *h_noise, unsigned P, int skip_wrapped,
+                         double *d_peaks, double *d_noise, void *stream);
+/* How the plan's last tspws_hip_ftan_rows / tspws_hip_ftan_coef call that did work went (all zero before the first one). */
+typedef struct {
+	unsigned rounds;   /* rounds of whole ensembles (ftan_coef: chunks of rows)                      */
+	unsigned rows;     /* rows that took part                                                        */
+	unsigned left_out; /* rows left out by h_mtr                                                     */
+	unsigned items;    /* work items of all classes: (scale, window or noise range, segment)         */
+	unsigned classes;  /* classes of ensembles with equal windows (and noise ranges, when used)      */
+} tspws_hip_ftan_stats;
+int  tspws_hip_ftan_rows_stats(const tspws_hip_plan *plan, tspws_hip_ftan_stats *stats);
+/* Host rule, no device: the windows of one station pair.  A surface wave of group velocity vmin .. vmax over the distance dist arrives at the
+ * lags dist / (vmax dt) .. dist / (vmin dt) samples: win[0] = [ceil(z + dist / (vmax dt)), floor(z + dist / (vmin dt)) + 1) clipped to [0, N];
+ * sides == 2 adds the mirrored acausal window win[1] = [ceil(z - dist / (vmin dt)), floor(z - dist / (vmax dt)) + 1).  win holds 2 sides
+ * entries.  A NULL win, sides other than 1 or 2, a non-finite argument, dist < 0, vmin <= 0, vmax < vmin, dt <= 0 and an empty window after
+ * clipping return TSPWS_E_ARG ("ftan_windows: ..."), nothing written. */
+int  tspws_ftan_windows(double dist, double vmin, double vmax, double dt, double z, size_t N, int sides, size_t *win);
+/* Host rule, no device: the period of every scale, T_s = 2 PI dt scale_s / w0 = 1 / fc_s of tspws_bands_from_frequencies (operations in
+ * that order), written to T[S].  A NULL scale / T (with S > 0) and dt or w0 <= 0 (or not finite) return TSPWS_E_ARG. */
+int  tspws_ftan_periods(const double *scale, unsigned S, double w0, double dt, double *T);
+
 /* ---- convergence curves ------------------------------------------------------------------------ */
 /* Similarity / misfit of the stack of the first i+1 traces against a reference, for i = 0..mtr-1
  * (ts_pws1f_lib.c:247-314, similarity :433-449, misfit :452-462).  d_ref_ts / d_ref_ls are [max] floats on the

@@ -23,7 +23,9 @@ on the plan's device, of a shape or of at least so many elements; ``_out`` and
 ``ts_out`` / ``mtr_out``, given or new), ``_sel`` (selections and masks),
 ``_coef_sets`` (``Y``), ``_strided_rows`` ([B][M][N] views of a wider base),
 ``_strided_refs`` ([B][N] reference rows likewise), ``_window``, ``_windows``
-(the (n0, n1) table) and ``_stats`` (the ``*_stats()`` dicts).
+(the (n0, n1) table), ``_ftan_tables`` (the per-ensemble windows, noise ranges
+and scale range of the group-arrival calls) and ``_stats`` (the ``*_stats()``
+dicts).
 """
 import ctypes as C
 import os
@@ -184,6 +186,11 @@ SYMBOLS = {
     "tspws_mwcs_bins": (_i, [_u, _d, _d, _d, _vp, _vp]),
     "tspws_hip_dtw_rows": (_i, [_vp, _vp, _sz, _u, _u, _vp, _vp, _sz, _d, _vp, _vp, _u, _vp, _vp, _vp]),
     "tspws_hip_dtw_rows_stats": (_i, [_vp, _vp]),
+    "tspws_hip_ftan_coef": (_i, [_vp, _vp, _vp, _sz, _u, _d, _u, _u, _vp, _u, _vp, _u, _i, _vp, _vp, _vp]),
+    "tspws_hip_ftan_rows": (_i, [_vp, _vp, _sz, _u, _u, _vp, _d, _u, _u, _vp, _u, _vp, _u, _i, _vp, _vp, _vp]),
+    "tspws_hip_ftan_rows_stats": (_i, [_vp, _vp]),
+    "tspws_ftan_windows": (_i, [_d, _d, _d, _d, _d, _sz, _i, _vp]),
+    "tspws_ftan_periods": (_i, [_vp, _u, _d, _d, _vp]),
     "tspws_mwcs_basis_size": (_sz, [_vp]),
     "tspws_mwcs_basis": (_i, [_vp, _vp]),
     "tspws_hip_selective_stack_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _i, _i, _d, _u, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1090,6 +1097,93 @@ class Plan:
         """How the last dtw_rows call with B, M > 0 went (tspws_hip_dtw_rows_stats): dict(rounds, rows, left_out, lags, samples)."""
         return self._stats("dtw_rows_stats", ("rounds", "rows", "left_out", "lags", "samples"))
 
+    def _ftan_tables(self, windows, noise, scales, B):
+        """The host tables of a group-arrival call: (windows uint64 [B][W][2], noise uint64 [B][2] or None, s_begin, s_end).  A (W, 2) window
+        array and a (q0, q1) noise pair are broadcast to all B ensembles; scales=None is every scale."""
+        import numpy as np
+        wa = np.asarray(windows)
+        if wa.ndim == 3:
+            if wa.shape[0] != B:
+                raise TspwsError(f"windows must be (W, 2) or ({B}, W, 2) pairs (n0, n1), got {wa.shape}")
+            wa = np.stack([self._windows(w) for w in wa]) if B else np.zeros((0,) + wa.shape[1:], np.uint64)
+        else:
+            one = self._windows(windows)
+            wa = np.broadcast_to(one, (B,) + one.shape)
+        wa = np.ascontiguousarray(wa, dtype=np.uint64)
+        na = None
+        if noise is not None:
+            na = np.asarray(noise)
+            if na.shape not in ((2,), (B, 2)) or na.dtype.kind not in "iu" or (na < 0).any():
+                raise TspwsError(f"noise must be None, a pair (q0, q1) or ({B}, 2) pairs of non-negative integers")
+            na = np.ascontiguousarray(np.broadcast_to(na, (B, 2)), dtype=np.uint64)
+        try:
+            s0, s1 = (0, self.S) if scales is None else (int(scales[0]), int(scales[1]))
+        except (TypeError, ValueError, IndexError):
+            raise TspwsError("scales must be None or a pair (s_begin, s_end)") from None
+        if not 0 <= s0 <= 0xFFFFFFFF or not 0 <= s1 <= 0xFFFFFFFF:
+            raise TspwsError("scales must be None or a pair (s_begin, s_end) of non-negative integers")
+        return wa, na, s0, s1
+
+    def _ftan_out(self, lead, W, Sx, P, noise, out, device):
+        """(peaks, noise or None) of a group-arrival call, given as `out` or new (NaN-filled): float64 tensors of at least
+        prod(lead) W Sx P 5 / prod(lead) Sx 2 values."""
+        import torch
+        n = 1
+        for k in lead:
+            n *= k
+        Sx, P = max(Sx, 0), max(int(P), 0)
+        o_peaks, o_noise = (out if noise else (out, None)) if out is not None else (None, None)
+        if out is None:
+            o_peaks = torch.full((*lead, W, Sx, P, 5), float("nan"), dtype=torch.float64, device=device)
+            o_noise = torch.full((*lead, Sx, 2), float("nan"), dtype=torch.float64, device=device) if noise else None
+        self._need(o_peaks, "out: peaks", "float64", n * W * Sx * P * 5, "tensor of >= {} values")
+        if noise:
+            self._need(o_noise, "out: noise", "float64", n * Sx * 2, "tensor of >= {} values")
+        return o_peaks, o_noise
+
+    def ftan_coef(self, Y, z, windows, scales=None, P=1, noise=None, ens=None, B=None, skip_wrapped=False, out=None):
+        """Group arrivals per scale from coefficient sets (tspws_hip_ftan_coef): `Y` [nrow][ncoef] (complex128, as for inverse: what forward
+        returns); `ens` = None (row i is ensemble i) or the uint32 [nrow] ensemble of every row, of `B` ensembles (None: max(ens) + 1).  `z` =
+        the zero-lag position in samples; `windows` = 1 to 4 pairs (n0, n1) for all ensembles, or [B][W][2] (see ftan_windows); `scales` =
+        (s_begin, s_end), None for all; `P` = 1 to 4 peaks; `noise` = None, a pair (q0, q1) or [B][2]; skip_wrapped leaves out the
+        coefficients whose filter support wraps round the trace ends.  Returns the peaks, float64 cuda [nrow][W][Sx][P][5] = tg (the group
+        arrival as a lag in samples), amp, re, im, k (unused slots: NaN and k = -1); with `noise` the pair (peaks, noise [nrow][Sx][2] = Q, n).
+        `out` as for wxs_rows.  New outputs hold NaN before the call.  Synchronises."""
+        import numpy as np
+        Y, _ = self._coef_sets(Y, "nrow")
+        nrow = Y.shape[0]
+        ens = _host_array(ens, "ens", np.uint32, (nrow,), optional=True)
+        B = (nrow if ens is None else int(ens.max()) + 1) if B is None else int(B)
+        wa, na, s0, s1 = self._ftan_tables(windows, noise, scales, B)
+        W = wa.shape[1]
+        o_peaks, o_noise = self._ftan_out((nrow,), W, s1 - s0, P, na is not None, out, Y.device)
+        check(self.lib.tspws_hip_ftan_coef(self.h, Y.data_ptr(), ens.ctypes.data if ens is not None else None, nrow, B, float(z), s0, s1, wa.ctypes.data, W,
+                                           na.ctypes.data if na is not None else None, int(P), int(bool(skip_wrapped)), o_peaks.data_ptr(),
+                                           o_noise.data_ptr() if na is not None else None, self._stream()), "ftan_coef")
+        return (o_peaks, o_noise) if na is not None else o_peaks
+
+    def ftan_rows(self, rows, z, windows, scales=None, P=1, noise=None, mtr=None, skip_wrapped=False, out=None):
+        """Group arrivals per scale from rows (tspws_hip_ftan_rows): `rows`, `z` and `mtr` as for wxs_rows (the [B][M][N] rows the batched
+        calls leave and their counts), the other arguments as for ftan_coef.  The rows are transformed on the device in rounds of whole
+        ensembles and never leave it.  Returns the peaks, float64 cuda [B][M][W][Sx][P][5] = tg, amp, re, im, k (unused slots and rows left
+        out: NaN and k = -1); with `noise` the pair (peaks, noise [B][M][Sx][2] = Q, n; rows left out: NaN and -1).  The M replicas of an
+        ensemble give the arrival's spread.  `out` as for wxs_rows.  New outputs hold NaN before the call.  Synchronises."""
+        import numpy as np
+        B, Mn, ld = self._strided_rows(rows)
+        wa, na, s0, s1 = self._ftan_tables(windows, noise, scales, B)
+        W = wa.shape[1]
+        mtr = _host_array(mtr, "mtr", np.uint32, (B, Mn), optional=True)
+        o_peaks, o_noise = self._ftan_out((B, Mn), W, s1 - s0, P, na is not None, out, rows.device)
+        if B and Mn:  # (an empty tensor has no address)
+            check(self.lib.tspws_hip_ftan_rows(self.h, rows.data_ptr(), ld, B, Mn, mtr.ctypes.data if mtr is not None else None, float(z), s0, s1,
+                                               wa.ctypes.data, W, na.ctypes.data if na is not None else None, int(P), int(bool(skip_wrapped)),
+                                               o_peaks.data_ptr(), o_noise.data_ptr() if na is not None else None, self._stream()), "ftan_rows")
+        return (o_peaks, o_noise) if na is not None else o_peaks
+
+    def ftan_rows_stats(self):
+        """How the last ftan_rows / ftan_coef call that did work went (tspws_hip_ftan_rows_stats): dict(rounds, rows, left_out, items, classes)."""
+        return self._stats("ftan_rows_stats", ("rounds", "rows", "left_out", "items", "classes"))
+
     def convergence(self, traces, ref_ts, ref_ls, steps=False):
         """Convergence curves of ONE ensemble (tspws_hip_convergence) on device tensors: `traces` float32 [mtr][N], `ref_ts` / `ref_ls`
         float32 [N] references of the ts-PWS / linear curve.  Returns (ts_sim, ts_misfit, ls_sim, ls_misfit) as float64 numpy [mtr]; with
@@ -1548,6 +1642,37 @@ def bands_from_frequencies(plan_or_tables, dt, edges, w0=None):
     check(load().tspws_bands_from_frequencies(scale.ctypes.data, scale.size, float(w), float(dt), lo.ctypes.data, hi.ctypes.data, lo.size,
                                              bands.ctypes.data, fc.ctypes.data), "bands_from_frequencies")
     return bands, fc
+
+
+def ftan_windows(dist, vmin, vmax, dt, z, N, sides=1):
+    """The windows of one station pair for Plan.ftan_rows (tspws_ftan_windows, host only): group velocities vmin .. vmax over the distance
+    `dist` arrive at the lags dist / (vmax dt) .. dist / (vmin dt) samples behind `z`; sides=2 adds the mirrored acausal window.  Returns
+    uint64 [sides][2]; an empty window after clipping to [0, N] is refused."""
+    import numpy as np
+    if sides not in (1, 2):
+        raise TspwsError("ftan_windows: sides must be 1 or 2")
+    win = np.zeros((sides, 2), np.uint64)
+    check(load().tspws_ftan_windows(float(dist), float(vmin), float(vmax), float(dt), float(z), int(N), int(sides), win.ctypes.data), "ftan_windows")
+    return win
+
+
+def ftan_periods(plan_or_tables, dt, w0=None):
+    """The period of every scale (tspws_ftan_periods, host only): T_s = 2 pi dt scale_s / w0, the inverse of bands_from_frequencies' fc.
+    `plan_or_tables` as there.  Returns T[S]."""
+    import numpy as np
+    if isinstance(plan_or_tables, Plan):
+        scale, w = plan_or_tables.tables()["scale"], plan_or_tables.info.w0
+    elif isinstance(plan_or_tables, dict):
+        scale, w = plan_or_tables["scale"], plan_or_tables.get("w0")
+    else:
+        scale, w = plan_or_tables
+    w = w0 if w0 is not None else w
+    if w is None:
+        raise TspwsError("ftan_periods needs w0")
+    scale = np.ascontiguousarray(scale, dtype=np.float64)
+    T = np.zeros(scale.size, np.float64)
+    check(load().tspws_ftan_periods(scale.ctypes.data, scale.size, float(w), float(dt), T.ctypes.data), "ftan_periods")
+    return T
 
 
 # tspws_weights_from_scores' rules, by name
