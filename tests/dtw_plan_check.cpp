@@ -9,7 +9,7 @@
 //   rounds      the rounds tile the ensembles in order; planes and table stay within the budget unless the round is one ensemble; a round that
 //               stops early could not have taken the next ensemble
 //   table       the block (allocated at its exact size: ASan sees any write past it) holds the slot of every row, numbering the participating
-//               rows of the round in order, DT_NOSLOT for the others
+//               rows of the round in order, NOSLOT for the others
 #include "dtw_plan.h"
 
 #include <cstdio>
@@ -83,9 +83,9 @@ static void check_rounds(const DtwPar &p, const std::vector<size_t> &win, size_t
 		for (size_t m = 0; m < M; m++) n += mtr[e * M + m] > 0;
 		nrows0[e + 1] = nrows0[e] + n;
 	}
-	const std::vector<DtwRound> rounds = dt_rounds(B, nrows0.data(), M, g, budget);
+	const std::vector<Round> rounds = dt_rounds(B, nrows0.data(), M, g, budget);
 	size_t next = 0;
-	for (const DtwRound &r : rounds) {
+	for (const Round &r : rounds) {
 		REQUIRE(r.j0 == next && r.j1 > r.j0 && r.j1 <= B);
 		next = r.j1;
 		const size_t nb = r.j1 - r.j0, nrows = nrows0[r.j1] - nrows0[r.j0];
@@ -104,7 +104,7 @@ static void check_rounds(const DtwPar &p, const std::vector<size_t> &win, size_t
 		for (size_t e = r.j0; e < r.j1; e++)
 			for (size_t m = 0; m < M; m++) {
 				const size_t i = (e - r.j0) * M + m;
-				if (mtr[e * M + m] == 0) { REQUIRE(slot_of[i] == DT_NOSLOT); continue; }
+				if (mtr[e * M + m] == 0) { REQUIRE(slot_of[i] == NOSLOT); continue; }
 				REQUIRE(slot < nrows && slot_of[i] == slot);
 				slot++;
 			}

@@ -147,9 +147,9 @@ static void check_plan(const Frame &f, unsigned s0, unsigned s1, const std::vect
 static void check_rounds(const Frame &f, const FtPlan &p, size_t B, size_t M, unsigned P, int pattern, size_t budget, std::mt19937_64 &rng)
 {
 	auto total = [&](size_t nb) { return ft_set_bytes(nb, M, f.ncoef) + ft_pass_bytes(p, P, nb * M); };
-	const std::vector<FtRound> rounds = ft_rounds(B, M, f.ncoef, p, P, budget);
+	const std::vector<Round> rounds = ft_rounds(B, M, f.ncoef, p, P, budget);
 	size_t next = 0;
-	for (const FtRound &r : rounds) {
+	for (const Round &r : rounds) {
 		REQUIRE(r.j0 == next && r.j1 > r.j0 && r.j1 <= B);
 		next = r.j1;
 		REQUIRE(total(r.j1 - r.j0) <= budget || r.j1 - r.j0 == 1);
@@ -157,8 +157,8 @@ static void check_rounds(const Frame &f, const FtPlan &p, size_t B, size_t M, un
 		// the table of the round, in a block of its exact size
 		const size_t nrows = (r.j1 - r.j0) * M;
 		std::vector<unsigned> ens(nrows);
-		for (size_t i = 0; i < nrows; i++) ens[i] = pattern == 2 || (pattern == 1 && rng() % 3 == 0) ? FT_NOSLOT : (unsigned)(r.j0 + i / M);
-		const size_t nslots = ft_count_slots(ens.data(), nrows);
+		for (size_t i = 0; i < nrows; i++) ens[i] = pattern == 2 || (pattern == 1 && rng() % 3 == 0) ? NOSLOT : (unsigned)(r.j0 + i / M);
+		const size_t nslots = count_slots(ens.data(), nrows);
 		const FtTab t = ft_tab(p, nslots, nrows);
 		const size_t off[9] = {t.items, t.tasks, t.classes, t.pspans, t.nspans, t.scales, t.list, t.slot_of, t.bytes};
 		const size_t size[8] = {p.items.size() * sizeof(FtItem), p.tasks.size() * sizeof(FtTask), p.classes.size() * sizeof(FtClass), p.pspans.size() * sizeof(FtSpan),
@@ -185,7 +185,7 @@ static void check_rounds(const Frame &f, const FtPlan &p, size_t B, size_t M, un
 		for (size_t i = 0; i < p.scales.size(); i++) REQUIRE(scales[i].base == p.scales[i].base && scales[i].D == p.scales[i].D && scales[i].Ns == p.scales[i].Ns);
 		size_t slot = 0;
 		for (size_t i = 0; i < nrows; i++) {
-			if (ens[i] == FT_NOSLOT) { REQUIRE(slot_of[i] == FT_NOSLOT); continue; }
+			if (ens[i] == NOSLOT) { REQUIRE(slot_of[i] == NOSLOT); continue; }
 			REQUIRE(slot < nslots && slot_of[i] == slot && list[slot].row == i && list[slot].cls == p.cls_of[ens[i]]);
 			// every partial entry a wave of this row writes lies inside the pass's partial block
 			const FtClass &cl = p.classes[list[slot].cls];

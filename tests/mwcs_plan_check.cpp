@@ -113,9 +113,9 @@ static void check_rounds(const MwPar &p, const std::vector<size_t> &win, size_t 
 		for (size_t m = 0; m < M; m++) n += mtr[e * M + m] > 0;
 		nrows0[e + 1] = nrows0[e] + n;
 	}
-	const std::vector<MwRound> rounds = mw_rounds(B, nrows0.data(), M, J, p, budget);
+	const std::vector<Round> rounds = mw_rounds(B, nrows0.data(), M, J, p, budget);
 	size_t next = 0;
-	for (const MwRound &r : rounds) {
+	for (const Round &r : rounds) {
 		REQUIRE(r.j0 == next && r.j1 > r.j0 && r.j1 <= B);
 		next = r.j1;
 		REQUIRE(mw_round_bytes(nrows0.data(), r.j0, r.j1, M, J, p) <= budget || r.j1 - r.j0 == 1);
@@ -150,7 +150,7 @@ static void check_rounds(const MwPar &p, const std::vector<size_t> &win, size_t 
 		for (size_t e = r.j0; e < r.j1; e++)
 			for (size_t m = 0; m < M; m++) {
 				const size_t i = (e - r.j0) * M + m;
-				if (mtr[e * M + m] == 0) { REQUIRE(slot_of[i] == MW_NOSLOT); continue; }
+				if (mtr[e * M + m] == 0) { REQUIRE(slot_of[i] == NOSLOT); continue; }
 				REQUIRE(slot < nrows && slot_of[i] == slot && srcs[slot].row == e * M + m && srcs[slot].bl == e - r.j0);
 				slot++;
 			}

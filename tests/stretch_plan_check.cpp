@@ -106,7 +106,7 @@ static void check_rounds(size_t B, size_t M, unsigned E, const std::vector<unsig
 				}
 			}
 			for (size_t m = 0; m < M; m++)
-				if (mtr && !((*mtr)[b * M + m] > 0)) REQUIRE(slot_of[(b - r.j0) * M + m] == SR_NOSLOT);
+				if (mtr && !((*mtr)[b * M + m] > 0)) REQUIRE(slot_of[(b - r.j0) * M + m] == NOSLOT);
 		}
 		REQUIRE(ti == nt && slot == nrows);
 	}

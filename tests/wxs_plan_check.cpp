@@ -70,7 +70,7 @@ static void check_plan(const Frame &f, const std::vector<WxBand> &bands, const s
 		bool in = false;
 		for (const WxBand &b : bands) in = in || (s >= b.s_begin && s < b.s_end);
 		if (in) { REQUIRE(u < p.used.size() && p.used[u] == s && p.uidx[s] == u); u++; }
-		else REQUIRE(p.uidx[s] == WX_NOSLOT);
+		else REQUIRE(p.uidx[s] == NOSLOT);
 	}
 	REQUIRE(u == p.used.size());
 	unsigned next = 0;
@@ -118,9 +118,9 @@ static void check_rounds(const Frame &f, const WxPlan &p, const std::vector<WxBa
 {
 	const unsigned R = (unsigned)bands.size();
 	auto total = [&](size_t nb) { return wx_set_bytes(nb, M, f.ncoef) + wx_pass_bytes(p, R, nb * M); };
-	const std::vector<WxRound> rounds = wx_rounds(B, M, f.ncoef, p, R, budget);
+	const std::vector<Round> rounds = wx_rounds(B, M, f.ncoef, p, R, budget);
 	size_t next = 0;
-	for (const WxRound &r : rounds) {
+	for (const Round &r : rounds) {
 		REQUIRE(r.j0 == next && r.j1 > r.j0 && r.j1 <= B);
 		next = r.j1;
 		REQUIRE(total(r.j1 - r.j0) <= budget || r.j1 - r.j0 == 1);
@@ -128,8 +128,8 @@ static void check_rounds(const Frame &f, const WxPlan &p, const std::vector<WxBa
 		// the table of the round, in a block of its exact size
 		const size_t nrows = (r.j1 - r.j0) * M;
 		std::vector<unsigned> ens(nrows);
-		for (size_t i = 0; i < nrows; i++) ens[i] = pattern == 2 || (pattern == 1 && rng() % 3 == 0) ? WX_NOSLOT : (unsigned)(i / M);
-		const size_t nslots = wx_count_slots(ens.data(), nrows);
+		for (size_t i = 0; i < nrows; i++) ens[i] = pattern == 2 || (pattern == 1 && rng() % 3 == 0) ? NOSLOT : (unsigned)(i / M);
+		const size_t nslots = count_slots(ens.data(), nrows);
 		const WxTab t = wx_tab(p, R, nslots, nrows);
 		const size_t off[8] = {t.items, t.tasks, t.spans, t.uidx, t.bands, t.list, t.slot_of, t.bytes};
 		const size_t size[7] = {p.items.size() * sizeof(WxItem), p.tasks.size() * sizeof(WxTask), p.spans.size() * sizeof(WxSpan), p.uidx.size() * sizeof(unsigned),
@@ -153,7 +153,7 @@ static void check_rounds(const Frame &f, const WxPlan &p, const std::vector<WxBa
 		for (unsigned i = 0; i < R; i++) REQUIRE(bd[i].s_begin == bands[i].s_begin && bd[i].s_end == bands[i].s_end);
 		size_t slot = 0;
 		for (size_t i = 0; i < nrows; i++) {
-			if (ens[i] == WX_NOSLOT) { REQUIRE(slot_of[i] == WX_NOSLOT); continue; }
+			if (ens[i] == NOSLOT) { REQUIRE(slot_of[i] == NOSLOT); continue; }
 			REQUIRE(slot < nslots && slot_of[i] == slot && list[slot].row == i && list[slot].ens == ens[i]);
 			slot++;
 		}

@@ -1,10 +1,14 @@
 // batch_host.h -- host code that the batched entry points share (batch.hip, jk_single.hip, jk_batch.hip, jk_batch_two_stage.hip, conv_batch.hip,
-// sub_batch.hip, boot_batch.hip, weighted_batch.hip): the lifetime of a call's uploads, the planning of rounds and finish batches, and the small loops
-// over a selection that every unit needs (the layout of a table block, TableLayout, is in column_runs.h).  Only what removes knowledge from its call sites lives here; the kernels they share are in batch_kernels.h,
-// and what sub_batch.hip, boot_batch.hip and weighted_batch.hip share beyond that -- their kernels, round driver and argument check -- in row_batch.h.
+// sub_batch.hip, boot_batch.hip, weighted_batch.hip) and the row-analysis units: the lifetime of a call's uploads, the planning of finish batches, and
+// the small loops over a selection that every unit needs.  Only what removes knowledge from its call sites lives here; the kernels they share are in
+// batch_kernels.h, and what sub_batch.hip, boot_batch.hip and weighted_batch.hip share beyond that -- their kernels, round driver and argument check --
+// in row_batch.h.  What needs no HIP runtime is in host_plan.h, which the CPU checks compile too: the layout of a table block (TableLayout), the
+// rounds of whole ensembles (Round, whole_ensemble_rounds), participation and slots, task packing and the range checks.  coef_rows.h, on top of
+// this header: the chunk and round drivers of the units that work on coefficient sets (wxs_rows.hip, ftan_rows.hip).
 #pragma once
 
 #include "tspws_internal.h"
+#include "host_plan.h"
 
 #include <deque>
 #include <unordered_map>
@@ -38,27 +42,15 @@ private:
 	std::deque<std::vector<char>> blocks_;
 };
 
+// an argument refused: "who: what" (what: the message tail that a check of the host plans returns)
+static inline int refuse(const char *who, const char *what) { return fail(TSPWS_E_ARG, (std::string(who) + ": " + what).c_str()); }
+
 // Rows of one finish batch: sets, reconstructions and the inverse's octave buffer of the batch within `budget` at per_row bytes a row
 // (tspws_inverse_row_bytes, times whatever shares the batch); even, so that the inverse pairs the same rows whatever the batching; at most
 // 65534 (grid.y of the epilogues) and `cap`
 static inline size_t even_rows_per_batch(size_t budget, size_t per_row, size_t cap)
 {
 	return std::min<size_t>({cap, 65534, std::max<size_t>(2, (budget / per_row) & ~(size_t)1)});
-}
-
-// Rounds of whole ensembles [j0, j1) of a list of n: the first ensemble of a round is always taken (one alone may exceed the budget), the
-// round extends while fits(j0, j1 + 1) says that the ensembles [j0, j1 + 1) fit together.
-struct Round { size_t j0, j1; };
-template <class Fits>
-static inline std::vector<Round> whole_ensemble_rounds(size_t n, Fits fits)
-{
-	std::vector<Round> rounds;
-	for (size_t j0 = 0, j1; j0 < n; j0 = j1) {
-		j1 = j0 + 1;
-		while (j1 < n && fits(j0, j1 + 1)) j1++;
-		rounds.push_back({j0, j1});
-	}
-	return rounds;
 }
 
 // kept traces of one row of a selection (bytes == 1)

@@ -11,10 +11,9 @@
 // the starts of all columns' pieces, and a run has one signature in every column.  Groups ascend along a column.
 #pragma once
 
-#include <algorithm>
-#include <cstddef>
+#include "host_plan.h" // TableLayout (the layout of the run tables' blocks)
+
 #include <cstring>
-#include <vector>
 
 struct Chunk { // one streaming work item of the partial-stack kernel
 	unsigned long long t0; // first local trace
@@ -28,20 +27,6 @@ struct RunDesc { // one run of consecutive traces with one signature, for k_rows
 	unsigned member, flush;  // bit c: the run belongs to column c / column c's group ends with this run
 	unsigned frow;           // first entry of the run's flush destinations in flush_rows (ascending column order)
 	unsigned pad[2];
-};
-
-// The layout of a table block: the arrays one after the other, each aligned for its element type.  A unit states its block ONCE, as a function of
-// the arrays' lengths; with upper bounds of the lengths the same function gives an upper bound of the block (add is monotone in count, whatever
-// came before), which is what plans the rounds of the batched calls.
-struct TableLayout {
-	size_t bytes = 0;
-	template <class T>
-	size_t add(size_t count) // offset of an array of `count` T
-	{
-		const size_t o = (bytes + alignof(T) - 1) / alignof(T) * alignof(T);
-		bytes = o + count * sizeof(T);
-		return o;
-	}
 };
 
 constexpr unsigned SIG_DELETED = ~0u; // (32-bit signatures: Kmax is an unsigned in t_tsPWS, any value is a legal group count)

@@ -12,15 +12,14 @@
 // the bits 2 (i % 16) of word i / 16; the plane of (row, range w) is words[w] = ceil(n_w / 16) rows of nlp words, [word][lag index].  A
 // participating row's planes lie range after range: range w at poff[w] words into its P = poff[W] words; slot s of the round at s P.
 // ROUNDS.  Whole ensembles whose participating rows' planes and table stay inside the parts budget; the first ensemble of a round is always
-// taken (one alone may exceed the budget).
+// taken (one alone may exceed the budget).  The round rule, participation, the slots and the range words are host_plan.h's.
 #pragma once
 
-#include "column_runs.h" // TableLayout
+#include "host_plan.h"
 
 #include <cstdint>
 
 enum { DT_WMAX = 4, DT_LMAX = 127, DT_BMAX = 8, DT_NMAX = 131072, DT_CHUNK = 64, DT_BACK = 8 }; // ..., samples per staged chunk, words per backtrack block
-constexpr unsigned DT_NOSLOT = ~0u;
 
 struct DtwPar { unsigned Lmax, b; }; // (tspws_dtw_par)
 
@@ -35,9 +34,7 @@ inline const char *dt_par_error(const DtwPar &p)
 // what is wrong with the W ranges win[2 w], win[2 w + 1] (NULL: nothing); needs no plan (n1 <= N is the caller's check)
 inline const char *dt_range_error(const size_t *win, unsigned W)
 {
-	if (!W || W > DT_WMAX) return "1 to 4 lag ranges";
-	for (unsigned w = 0; w < W; w++)
-		if (win[2 * w] >= win[2 * w + 1]) return "an empty lag range (n0 >= n1)";
+	if (const char *e = range_error(win, W, LAG_RANGES)) return e;
 	for (unsigned w = 0; w < W; w++)
 		if (win[2 * w + 1] - win[2 * w] > DT_NMAX) return "a lag range longer than 131072 samples";
 	return nullptr;
@@ -93,7 +90,7 @@ inline DtwLds dt_lds(const DtwPar &p, unsigned Q)
 	return o;
 }
 
-// the table block of a round: slot of every (ensemble of the round, m) or DT_NOSLOT
+// the table block of a round: slot of every (ensemble of the round, m) or NOSLOT
 struct DtwTab { size_t slot_of, bytes; };
 inline DtwTab dt_tab(size_t nall)
 {
@@ -105,33 +102,19 @@ inline DtwTab dt_tab(size_t nall)
 }
 
 inline size_t dt_plane_bytes(size_t nrows, const DtwGeom &g) { return nrows * (size_t)g.P() * sizeof(unsigned); }
-// nrows0[b] = participating rows in front of ensemble b (B + 1 entries)
+// nrows0: participating_rows0
 inline size_t dt_round_bytes(const size_t *nrows0, size_t j0, size_t j1, size_t M, const DtwGeom &g)
 {
 	return dt_plane_bytes(nrows0[j1] - nrows0[j0], g) + dt_tab((j1 - j0) * M).bytes;
 }
 
-struct DtwRound { size_t j0, j1; };
-inline std::vector<DtwRound> dt_rounds(size_t B, const size_t *nrows0, size_t M, const DtwGeom &g, size_t budget)
+inline std::vector<Round> dt_rounds(size_t B, const size_t *nrows0, size_t M, const DtwGeom &g, size_t budget)
 {
-	std::vector<DtwRound> rounds;
-	for (size_t j0 = 0, j1; j0 < B; j0 = j1) {
-		j1 = j0 + 1;
-		while (j1 < B && dt_round_bytes(nrows0, j0, j1 + 1, M, g) <= budget) j1++;
-		rounds.push_back({j0, j1});
-	}
-	return rounds;
+	return whole_ensemble_rounds(B, [&](size_t j0, size_t j1) { return dt_round_bytes(nrows0, j0, j1, M, g) <= budget; });
 }
 
 // the table of round r into blob (dt_tab's layout with the round's own counts; zeroed by the caller); returns the participating rows
-inline size_t dt_fill_round(char *blob, const DtwTab &t, const DtwRound &r, size_t M, const unsigned *h_mtr)
+inline size_t dt_fill_round(char *blob, const DtwTab &t, const Round &r, size_t M, const unsigned *h_mtr)
 {
-	unsigned *slot_of = (unsigned *)(blob + t.slot_of);
-	size_t slot = 0;
-	for (size_t e = r.j0; e < r.j1; e++)
-		for (size_t m = 0; m < M; m++) {
-			const bool in = !h_mtr || h_mtr[e * M + m] > 0;
-			slot_of[(e - r.j0) * M + m] = in ? (unsigned)slot++ : DT_NOSLOT;
-		}
-	return slot;
+	return fill_round_slots((unsigned *)(blob + t.slot_of), r, M, h_mtr, [](size_t, size_t, size_t) {});
 }

@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(64) k_dtw(const float *__restrict__ rows, size
 
 	const float *__restrict__ cp = rows + row * ld;
 	const float *__restrict__ rp = ref + (row / M) * ldr;
-	bool dead = slot == DT_NOSLOT;
+	bool dead = slot == NOSLOT;
 	double ac = 0.0, ar = 0.0;
 	if (!dead) { // (wave-uniform)
 		bool badc, badr;
@@ -304,29 +304,23 @@ extern "C" int tspws_hip_dtw_rows(tspws_hip_plan *pl, const float *d_rows, size_
 	// first what needs no plan
 	if (!d_rows || !d_ref || !par || !h_win || !d_fit) return fail(TSPWS_E_ARG, "dtw_rows: NULL");
 	const DtwPar P = {par->Lmax, par->b};
-	if (const char *e = dt_par_error(P)) return fail(TSPWS_E_ARG, (std::string("dtw_rows: ") + e).c_str());
-	if (const char *e = dt_range_error(h_win, W)) return fail(TSPWS_E_ARG, (std::string("dtw_rows: ") + e).c_str());
+	if (const char *e = dt_par_error(P)) return refuse("dtw_rows", e);
+	if (const char *e = dt_range_error(h_win, W)) return refuse("dtw_rows", e);
 	if (!std::isfinite(z)) return fail(TSPWS_E_ARG, "dtw_rows: a NaN or infinite zero-lag position");
 	if (!pl) return fail(TSPWS_E_ARG, "dtw_rows: NULL");
 	const size_t N = pl->N;
 	if (ld < N) return fail(TSPWS_E_ARG, "dtw_rows: row stride below the trace length");
 	if (ldr < N) return fail(TSPWS_E_ARG, "dtw_rows: reference row stride below the trace length");
-	for (unsigned w = 0; w < W; w++)
-		if (h_win[2 * w + 1] > N) return fail(TSPWS_E_ARG, "dtw_rows: a lag range past the trace length");
+	if (const char *e = range_past_error(h_win, W, N, LAG_RANGES)) return refuse("dtw_rows", e);
 	if (!B || !M) return 0;
 	if ((unsigned long long)B * M > 0xfffffff0ull) return fail(TSPWS_E_ARG, "dtw_rows: more than 2^32 - 16 rows");
 
 	const DtwGeom g = dt_geom(P, h_win, W);
 	const DtwLds lds = dt_lds(P, g.Q);
-	std::vector<size_t> nrows0((size_t)B + 1, 0); // participating rows in front of ensemble b
-	for (unsigned b = 0; b < B; b++) {
-		size_t n = M;
-		if (h_mtr) { n = 0; for (unsigned m = 0; m < M; m++) n += h_mtr[(size_t)b * M + m] > 0; }
-		nrows0[b + 1] = nrows0[b] + n;
-	}
-	const std::vector<DtwRound> rounds = dt_rounds(B, nrows0.data(), M, g, tspws_part_budget_bytes());
+	const std::vector<size_t> nrows0 = participating_rows0(h_mtr, B, M);
+	const std::vector<Round> rounds = dt_rounds(B, nrows0.data(), M, g, tspws_part_budget_bytes());
 	size_t max_tab = 0, max_planes = 0;
-	for (const DtwRound &r : rounds) {
+	for (const Round &r : rounds) {
 		if ((unsigned long long)(r.j1 - r.j0) * M * W > 0x7fffffffull) return fail(TSPWS_E_ARG, "dtw_rows: more than 2^31 waves in a round");
 		max_tab = std::max(max_tab, dt_tab((r.j1 - r.j0) * (size_t)M).bytes);
 		max_planes = std::max(max_planes, dt_plane_bytes(nrows0[r.j1] - nrows0[r.j0], g));
@@ -348,7 +342,7 @@ extern "C" int tspws_hip_dtw_rows(tspws_hip_plan *pl, const float *d_rows, size_
 	void *v;
 	if ((rc = scratch(pl, SCR_DTP, std::max<size_t>(max_planes, 16), &v))) return rc; // (the largest round's: the slot does not grow between rounds)
 	unsigned *planes = (unsigned *)v;
-	for (const DtwRound &r : rounds) {
+	for (const Round &r : rounds) {
 		const size_t nb = r.j1 - r.j0;
 		stats.rounds++;
 		const DtwTab o = dt_tab(nb * M);

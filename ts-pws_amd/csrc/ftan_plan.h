@@ -15,14 +15,14 @@
 // its own result (WX_TASK's principle).  A pass runs max_tasks waves per participating row; a row of a class with fewer tasks ends the rest.
 // ROUNDS.  tspws_hip_ftan_rows: whole ensembles whose M coefficient sets, partial results and table stay inside the parts budget; the first
 // ensemble of a round is always taken.  tspws_hip_ftan_coef (the sets are the caller's): chunks of rows whose partial results and table do.
+// The round rule, the slots, the chunk search and the task packing are host_plan.h's.
 #pragma once
 
-#include "wxs_plan.h" // WxScale, wx_k_range, TableLayout
+#include "wxs_plan.h" // WxScale, wx_k_range; host_plan.h
 
 #include <map>
 
 enum { FT_SEG = 256, FT_TASK = 16, FT_WMAX = 4, FT_PMAX = 4 };
-constexpr unsigned FT_NOSLOT = ~0u;
 
 // members [k0, k0 + count) of a scale of Ns coefficients that starts at `base` of a row's set; noise != 0: an item of the noise range
 struct FtItem { unsigned long long base; unsigned k0, count, Ns, noise; };
@@ -77,13 +77,8 @@ inline FtPlan ft_plan(const WxScale *sc, unsigned S, size_t N, unsigned s_begin,
 		if (noise)
 			for (unsigned s = s_begin; s < s_end; s++) p.nspans.push_back(cut(sc[s], noise[2 * b], noise[2 * b + 1], 1));
 		cl.nitems = (unsigned)p.items.size() - cl.item0;
-		unsigned passes = 0;
-		for (unsigned i = cl.item0; i < cl.item0 + cl.nitems; i++) {
-			const unsigned n = (p.items[i].count + 63) / 64;
-			if (i == cl.item0 || passes + n > FT_TASK) { p.tasks.push_back({i, 0}); passes = 0; }
-			p.tasks.back().n++;
-			passes += n;
-		}
+		pack_tasks(p.tasks, cl.item0, cl.item0 + cl.nitems, FT_TASK, [&](unsigned i) { return (p.items[i].count + 63) / 64; },
+		           [&](unsigned i) { return i == cl.item0; }); // (no task crosses a class)
 		cl.ntasks = (unsigned)p.tasks.size() - cl.task0;
 		p.classes.push_back(cl);
 		p.max_items = std::max(p.max_items, cl.nitems);
@@ -93,7 +88,7 @@ inline FtPlan ft_plan(const WxScale *sc, unsigned S, size_t N, unsigned s_begin,
 }
 
 // the table block of a pass over nrows rows of which nslots take part:
-// items | tasks | classes | peak spans | noise spans | scales | the participating rows | slot of every row or FT_NOSLOT
+// items | tasks | classes | peak spans | noise spans | scales | the participating rows | slot of every row or NOSLOT
 struct FtTab { size_t items, tasks, classes, pspans, nspans, scales, list, slot_of, bytes; };
 inline FtTab ft_tab(const FtPlan &p, size_t nslots, size_t nrows)
 {
@@ -113,44 +108,23 @@ inline size_t ft_pass_bytes(const FtPlan &p, unsigned P, size_t nrows) { return 
 // the coefficient sets of nb ensembles of M rows
 inline size_t ft_set_bytes(size_t nb, size_t M, size_t ncoef) { return nb * M * ncoef * 2 * sizeof(double); }
 
-struct FtRound { size_t j0, j1; };
-
 // tspws_hip_ftan_rows: rounds of whole ensembles
-inline std::vector<FtRound> ft_rounds(size_t B, size_t M, size_t ncoef, const FtPlan &p, unsigned P, size_t budget)
+inline std::vector<Round> ft_rounds(size_t B, size_t M, size_t ncoef, const FtPlan &p, unsigned P, size_t budget)
 {
-	std::vector<FtRound> rounds;
-	auto fits = [&](size_t nb) {
-		const size_t a = ft_set_bytes(nb, M, ncoef), b = ft_pass_bytes(p, P, nb * M);
+	return whole_ensemble_rounds(B, [&](size_t j0, size_t j1) {
+		const size_t a = ft_set_bytes(j1 - j0, M, ncoef), b = ft_pass_bytes(p, P, (j1 - j0) * M);
 		return a <= budget && b <= budget - a;
-	};
-	for (size_t j0 = 0, j1; j0 < B; j0 = j1) {
-		j1 = j0 + 1;
-		while (j1 < B && fits(j1 + 1 - j0)) j1++;
-		rounds.push_back({j0, j1});
-	}
-	return rounds;
+	});
 }
 
-// tspws_hip_ftan_coef: the rows of a chunk (at least one)
+// tspws_hip_ftan_coef: the rows of a chunk (at least one; ft_pass_bytes is monotone in the rows)
 inline size_t ft_chunk_rows(size_t nrow, const FtPlan &p, unsigned P, size_t budget)
 {
-	size_t lo = 1, hi = nrow; // the largest n in [1, nrow] whose pass fits (ft_pass_bytes is monotone in n)
-	while (lo < hi) {
-		const size_t mid = lo + (hi - lo + 1) / 2;
-		if (ft_pass_bytes(p, P, mid) <= budget) lo = mid; else hi = mid - 1;
-	}
-	return lo;
-}
-
-inline size_t ft_count_slots(const unsigned *ens, size_t nrows)
-{
-	size_t n = 0;
-	for (size_t i = 0; i < nrows; i++) n += ens[i] != FT_NOSLOT;
-	return n;
+	return largest_fitting(nrow, [&](size_t n) { return ft_pass_bytes(p, P, n); }, budget);
 }
 
 // the table of a pass into blob (ft_tab's layout for the pass's own counts; zeroed by the caller); ens[nrows] = the ensemble (of the call's B)
-// of every row, or FT_NOSLOT for a row that does not take part.  Returns the participating rows.
+// of every row, or NOSLOT for a row that does not take part.  Returns the participating rows.
 inline size_t ft_fill(char *blob, const FtTab &t, const FtPlan &p, const unsigned *ens, size_t nrows)
 {
 	std::copy(p.items.begin(), p.items.end(), (FtItem *)(blob + t.items));
@@ -160,11 +134,5 @@ inline size_t ft_fill(char *blob, const FtTab &t, const FtPlan &p, const unsigne
 	std::copy(p.nspans.begin(), p.nspans.end(), (FtSpan *)(blob + t.nspans));
 	std::copy(p.scales.begin(), p.scales.end(), (FtScale *)(blob + t.scales));
 	FtRow *list = (FtRow *)(blob + t.list);
-	unsigned *slot_of = (unsigned *)(blob + t.slot_of);
-	size_t slot = 0;
-	for (size_t i = 0; i < nrows; i++) {
-		slot_of[i] = ens[i] == FT_NOSLOT ? FT_NOSLOT : (unsigned)slot;
-		if (ens[i] != FT_NOSLOT) list[slot++] = {(unsigned)i, p.cls_of[ens[i]]};
-	}
-	return slot;
+	return fill_row_slots((unsigned *)(blob + t.slot_of), ens, nrows, [&](size_t slot, unsigned e, size_t i) { list[slot] = {(unsigned)i, p.cls_of[e]}; });
 }

@@ -20,7 +20,7 @@
 // the wrap rule alone: a repeated call is bit-identical, and B, M, the other windows, scales and ensembles, P, the rounds and the padding
 // change no bit.
 #include "tspws_internal.h"
-#include "batch_host.h"
+#include "coef_rows.h"
 #include "lane_reduce.h"
 #include "ftan_plan.h"
 
@@ -140,7 +140,7 @@ __global__ void __launch_bounds__(256) k_ft_final(const double2 *__restrict__ Y,
 		const size_t row = (size_t)(on / Sx);
 		double *__restrict__ no = noise + ((size_t)row0 * Sx + on) * 2;
 		const unsigned slot = slot_of[row];
-		if (slot == FT_NOSLOT) { no[0] = nan; no[1] = -1.0; return; }
+		if (slot == NOSLOT) { no[0] = nan; no[1] = -1.0; return; }
 		const FtRow rw = list[slot];
 		const FtClass cl = classes[rw.cls];
 		const FtSpan sp = nspans[(size_t)rw.cls * Sx + sx];
@@ -161,7 +161,7 @@ __global__ void __launch_bounds__(256) k_ft_final(const double2 *__restrict__ Y,
 	unsigned long long bk[4] = {0, 0, 0, 0}, bi[4] = {0, 0, 0, 0}; // the first peaks so far, by (a2 decreasing, k increasing)
 	const double2 *__restrict__ ys = Y;
 	unsigned D = 0;
-	if (slot != FT_NOSLOT) {
+	if (slot != NOSLOT) {
 		const FtRow rw = list[slot];
 		const FtClass cl = classes[rw.cls];
 		const FtSpan sp = pspans[((size_t)rw.cls * Sx + sx) * W + w];
@@ -206,21 +206,19 @@ static int ft_check(const tspws_hip_plan *pl, const char *who, unsigned long lon
 {
 	const std::string w(who);
 	if (!pl) {
-		if (!W || W > FT_WMAX) return fail(TSPWS_E_ARG, (w + ": 1 to 4 windows").c_str());
+		if (const char *e = range_count_error(W, WINDOWS)) return refuse(who, e);
 		if (!P || P > FT_PMAX) return fail(TSPWS_E_ARG, (w + ": 1 to 4 peaks").c_str());
 		if (s_begin >= s_end) return fail(TSPWS_E_ARG, (w + ": an empty scale range (s_begin >= s_end)").c_str());
 		if (d_noise && !noise) return fail(TSPWS_E_ARG, (w + ": a noise output without a noise range").c_str());
 		if (!std::isfinite(z)) return fail(TSPWS_E_ARG, (w + ": a NaN or infinite zero-lag position").c_str());
 		if (nrows > 0xfffffff0ull) return fail(TSPWS_E_ARG, (w + ": more than 2^32 - 16 rows").c_str()); // (from the counts alone: before a table is read)
-		for (size_t i = 0; i < (size_t)B * W; i++)
-			if (win[2 * i] >= win[2 * i + 1]) return fail(TSPWS_E_ARG, (w + ": an empty window (n0 >= n1)").c_str());
+		if (const char *e = range_empty_error(win, (size_t)B * W, WINDOWS)) return refuse(who, e);
 		for (size_t b = 0; noise && b < B; b++)
 			if (noise[2 * b] >= noise[2 * b + 1]) return fail(TSPWS_E_ARG, (w + ": an empty noise range (q0 >= q1)").c_str());
 		return 0;
 	}
 	if (s_end > pl->S) return fail(TSPWS_E_ARG, (w + ": the scale range ends behind the last scale").c_str());
-	for (size_t i = 0; i < (size_t)B * W; i++)
-		if (win[2 * i + 1] > pl->N) return fail(TSPWS_E_ARG, (w + ": a window past the trace length").c_str());
+	if (const char *e = range_past_error(win, (size_t)B * W, pl->N, WINDOWS)) return refuse(who, e);
 	for (size_t b = 0; noise && b < B; b++)
 		if (noise[2 * b + 1] > pl->N) return fail(TSPWS_E_ARG, (w + ": a noise range past the trace length").c_str());
 	return 0;
@@ -228,20 +226,16 @@ static int ft_check(const tspws_hip_plan *pl, const char *who, unsigned long lon
 
 static FtPlan ft_plan_of(const tspws_hip_plan *pl, unsigned s_begin, unsigned s_end, const size_t *win, unsigned W, const size_t *noise, size_t B, int skip_wrapped)
 {
-	std::vector<WxScale> sc(pl->S);
-	for (unsigned s = 0; s < pl->S; s++) {
-		const ScaleDesc &d = pl->sc[s];
-		sc[s] = {d.L, d.D, d.Ns, d.c, d.coef_off, 0.0};
-	}
-	return ft_plan(sc.data(), pl->S, pl->N, s_begin, s_end, win, W, noise, B, skip_wrapped);
+	return ft_plan(wx_scales_of(pl).data(), pl->S, pl->N, s_begin, s_end, win, W, noise, B, skip_wrapped);
 }
 
-// one pass: the rows [0, nrows) of Y, ens[.] = the ensemble of every row (FT_NOSLOT: the row does not take part); outputs from row `row0` on
+// one pass: the rows [0, nrows) of Y, ens[.] = the ensemble of every row (NOSLOT: the row does not take part); outputs from row `row0` on;
+// the slots are reserved for a pass of max_rows rows
 static int ft_pass(tspws_hip_plan *pl, BatchCall &call, const char *who, const FtPlan &F, unsigned P, const double2 *Y, const unsigned *ens, size_t nrows,
-                   size_t row0, double z, size_t max_tab, size_t max_part, double *d_peaks, double *d_noise)
+                   size_t row0, double z, size_t max_rows, double *d_peaks, double *d_noise)
 {
 	hipStream_t st = call.stream();
-	const size_t nslots = ft_count_slots(ens, nrows);
+	const size_t nslots = count_slots(ens, nrows), max_tab = ft_tab(F, max_rows, max_rows).bytes, max_part = ft_part_bytes(F, P, max_rows);
 	const FtTab o = ft_tab(F, nslots, nrows);
 	const unsigned long long nwork = (unsigned long long)nslots * F.max_tasks, npk = (unsigned long long)nrows * F.W * F.Sx,
 	                         nout = npk + (d_noise ? (unsigned long long)nrows * F.Sx : 0);
@@ -288,19 +282,10 @@ extern "C" int tspws_hip_ftan_coef(tspws_hip_plan *pl, const double *d_Y, const 
 	HIP_TRY(hipSetDevice(pl->device));
 	BatchCall call(S_(s));
 	ft_stats_begin(pl, F);
-	pl->ftan_stats.rows = (unsigned)nrow;
-	std::vector<unsigned> ens(std::min(chunk, nrow));
-	for (size_t r0 = 0; r0 < nrow; r0 += chunk) {
-		const size_t n = std::min(chunk, nrow - r0);
-		for (size_t i = 0; i < n; i++) ens[i] = h_ens ? h_ens[r0 + i] : (unsigned)(r0 + i);
-		pl->ftan_stats.rounds++;
-		if (int rc = ft_pass(pl, call, who, F, P, (const double2 *)d_Y + r0 * pl->ncoef, ens.data(), n, r0, z, ft_tab(F, chunk, chunk).bytes,
-		                     ft_part_bytes(F, P, std::min(chunk, nrow)), d_peaks, d_noise))
-			return rc;
-	}
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(call.drain()); // outputs complete
-	return 0;
+	return coef_chunks(call, row_counters(pl->ftan_stats), (const double2 *)d_Y, nullptr, pl->ncoef, h_ens, nrow, chunk,
+	                   [&](const double2 *Y, const double2 *, const unsigned *ens, size_t n, size_t row0, size_t max_rows) {
+		                   return ft_pass(pl, call, who, F, P, Y, ens, n, row0, z, max_rows, d_peaks, d_noise);
+	                   });
 }
 
 extern "C" int tspws_hip_ftan_rows(tspws_hip_plan *pl, const float *d_rows, size_t ld, unsigned B, unsigned M, const unsigned *h_mtr, double z, unsigned s_begin,
@@ -316,38 +301,14 @@ extern "C" int tspws_hip_ftan_rows(tspws_hip_plan *pl, const float *d_rows, size
 	if (!B || !M) return 0;
 
 	const FtPlan F = ft_plan_of(pl, s_begin, s_end, h_win, W, d_noise ? h_noise : nullptr, B, skip_wrapped);
-	const size_t ncoef = pl->ncoef;
-	const std::vector<FtRound> rounds = ft_rounds(B, M, ncoef, F, P, tspws_part_budget_bytes());
-	size_t max_nb = 0;
-	for (const FtRound &r : rounds) max_nb = std::max(max_nb, r.j1 - r.j0);
+	const std::vector<Round> rounds = ft_rounds(B, M, pl->ncoef, F, P, tspws_part_budget_bytes());
 	HIP_TRY(hipSetDevice(pl->device));
-	hipStream_t st = S_(s);
-	BatchCall call(st);
+	BatchCall call(S_(s));
 	ft_stats_begin(pl, F);
-	int rc;
-	void *v;
-	if ((rc = scratch(pl, SCR_FTY, std::max<size_t>(ft_set_bytes(max_nb, M, ncoef), 16), &v))) return rc; // (the largest round's: the slot does not grow between rounds)
-	double2 *Y = (double2 *)v;
-	std::vector<unsigned> ens(max_nb * M);
-	for (const FtRound &r : rounds) {
-		const size_t nb = r.j1 - r.j0, nrows = nb * M;
-		// the rows left out are transformed too: ONE forward call on the round's rows
-		if ((rc = tspws_hip_forward_f32(pl, d_rows + r.j0 * M * ld, nrows, ld, (double *)Y, st))) return rc;
-		for (size_t bl = 0; bl < nb; bl++)
-			for (size_t m = 0; m < M; m++) {
-				const bool in = !h_mtr || h_mtr[(r.j0 + bl) * M + m] > 0;
-				ens[bl * M + m] = in ? (unsigned)(r.j0 + bl) : FT_NOSLOT;
-				pl->ftan_stats.rows += in;
-				pl->ftan_stats.left_out += !in;
-			}
-		pl->ftan_stats.rounds++;
-		if ((rc = ft_pass(pl, call, who, F, P, Y, ens.data(), nrows, r.j0 * M, z, ft_tab(F, max_nb * M, max_nb * M).bytes, ft_part_bytes(F, P, max_nb * M), d_peaks,
-		                  d_noise)))
-			return rc;
-	}
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(call.drain()); // outputs complete
-	return 0;
+	return coef_rounds(pl, call, row_counters(pl->ftan_stats), d_rows, ld, M, h_mtr, nullptr, 0, 0, rounds, SCR_FTY,
+	                   [&](const double2 *Y, const double2 *, const unsigned *ens, size_t n, size_t row0, size_t max_rows) {
+		                   return ft_pass(pl, call, who, F, P, Y, ens, n, row0, z, max_rows, d_peaks, d_noise);
+	                   });
 }
 
 extern "C" int tspws_hip_ftan_rows_stats(const tspws_hip_plan *pl, tspws_hip_ftan_stats *stats)

@@ -10,16 +10,17 @@
 // [nrows, nrows + nb)); an item is (source, window), numbered slot J + j.  A wave of the contraction takes MW_ROWS consecutive items: an item's
 // spectrum depends on its own samples alone, so a tile may straddle rows, ensembles and ranges.
 // ROUNDS.  Whole ensembles whose spectra ((rows + 1) J Qp doubles each), per-window results (rows J 3 doubles) and table stay inside the parts
-// budget; the first ensemble of a round is always taken (one alone may exceed the budget).
+// budget; the first ensemble of a round is always taken (one alone may exceed the budget).  The round rule, participation, the slots and the
+// range words are host_plan.h's.
 #pragma once
 
-#include "column_runs.h" // TableLayout
+#include "host_plan.h"
 
 #include <cmath>
 #include <cstdint>
 
 enum { MW_WMAX = 4, MW_JMAX = 4096, MW_QMAX = 64, MW_LMIN = 16, MW_LMAX = 1024, MW_PMAX = 4096, MW_HMAX = 8, MW_ROWS = 32, MW_CT = 16, MW_NT = 4 };
-constexpr unsigned MW_NOSLOT = ~0u, MW_REF = ~0u;
+constexpr unsigned MW_REF = ~0u;
 
 struct MwPar { unsigned L, hop, P, q0, q1, h; double taper, min_coh, max_err, max_delta, err_floor; }; // (tspws_mwcs_par)
 struct MwBins { unsigned qa, qb, Qx, Qp, Lp; }; // Qp: padded columns, Lp: L rounded up to 16 (the table's rows past L are zero)
@@ -128,7 +129,7 @@ inline void mw_basis(const MwPar &p, double *tab)
 
 // ---- the table block of a round ------------------------------------------------------------------------------------------------------
 // Bt[Qp][Lp] (column c < Qx: C[.][c]; Qx <= c < 2 Qx: S[.][c - Qx]; the rest and the rows past L zero) | T[Qp] (Tc | Ts | zero) | k[2 h + 1] | v[Qx] |
-// windows | sources | slot of every (ensemble of the round, m) or MW_NOSLOT
+// windows | sources | slot of every (ensemble of the round, m) or NOSLOT
 struct MwTab { size_t bt, T, k, v, wins, srcs, slot_of, bytes; };
 inline MwTab mw_tab(const MwPar &p, size_t J, size_t nsrc, size_t nall)
 {
@@ -144,28 +145,21 @@ inline MwTab mw_tab(const MwPar &p, size_t J, size_t nsrc, size_t nall)
 // the device blocks of a round, in bytes: the spectra F[slot J + j][Qp] of rows and references, the results win[slot J + j][3] of the rows
 inline size_t mw_spec_bytes(size_t nb, size_t nrows, size_t J, const MwBins &b) { return (nrows + nb) * J * b.Qp * sizeof(double); }
 inline size_t mw_win_bytes(size_t nrows, size_t J) { return nrows * J * 3 * sizeof(double); }
-// nrows0[b] = participating rows in front of ensemble b (B + 1 entries)
+// nrows0: participating_rows0
 inline size_t mw_round_bytes(const size_t *nrows0, size_t j0, size_t j1, size_t M, size_t J, const MwPar &p)
 {
 	const size_t nb = j1 - j0, nrows = nrows0[j1] - nrows0[j0];
 	return mw_spec_bytes(nb, nrows, J, mw_bins(p)) + mw_win_bytes(nrows, J) + mw_tab(p, J, nrows + nb, nb * M).bytes;
 }
 
-struct MwRound { size_t j0, j1; };
-inline std::vector<MwRound> mw_rounds(size_t B, const size_t *nrows0, size_t M, size_t J, const MwPar &p, size_t budget)
+inline std::vector<Round> mw_rounds(size_t B, const size_t *nrows0, size_t M, size_t J, const MwPar &p, size_t budget)
 {
-	std::vector<MwRound> rounds;
-	for (size_t j0 = 0, j1; j0 < B; j0 = j1) {
-		j1 = j0 + 1;
-		while (j1 < B && mw_round_bytes(nrows0, j0, j1 + 1, M, J, p) <= budget) j1++;
-		rounds.push_back({j0, j1});
-	}
-	return rounds;
+	return whole_ensemble_rounds(B, [&](size_t j0, size_t j1) { return mw_round_bytes(nrows0, j0, j1, M, J, p) <= budget; });
 }
 
 // the table of round r into blob (mw_tab's layout with the round's own counts; zeroed by the caller); basis: mw_basis's table.  Returns the
 // participating rows.
-inline size_t mw_fill_round(char *blob, const MwTab &t, const MwRound &r, size_t M, const unsigned *h_mtr, const MwPar &p, const double *basis, const MwWins &wl)
+inline size_t mw_fill_round(char *blob, const MwTab &t, const Round &r, size_t M, const unsigned *h_mtr, const MwPar &p, const double *basis, const MwWins &wl)
 {
 	const MwBins b = mw_bins(p);
 	const MwBasis o = mw_basis_layout(p);
@@ -182,14 +176,8 @@ inline size_t mw_fill_round(char *blob, const MwTab &t, const MwRound &r, size_t
 	std::copy(basis + o.v, basis + o.v + b.Qx, (double *)(blob + t.v));
 	std::copy(wl.wins.begin(), wl.wins.end(), (MwWin *)(blob + t.wins));
 	MwSrc *srcs = (MwSrc *)(blob + t.srcs);
-	unsigned *slot_of = (unsigned *)(blob + t.slot_of);
-	size_t slot = 0;
-	for (size_t e = r.j0; e < r.j1; e++)
-		for (size_t m = 0; m < M; m++) {
-			const bool in = !h_mtr || h_mtr[e * M + m] > 0;
-			slot_of[(e - r.j0) * M + m] = in ? (unsigned)slot : MW_NOSLOT;
-			if (in) srcs[slot++] = {(unsigned)(e * M + m), (unsigned)(e - r.j0)};
-		}
+	const size_t slot = fill_round_slots((unsigned *)(blob + t.slot_of), r, M, h_mtr,
+	                                     [&](size_t s, size_t e, size_t m) { srcs[s] = {(unsigned)(e * M + m), (unsigned)(e - r.j0)}; });
 	for (size_t e = r.j0; e < r.j1; e++) srcs[slot + (e - r.j0)] = {(unsigned)e, MW_REF};
 	return slot;
 }

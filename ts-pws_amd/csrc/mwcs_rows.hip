@@ -215,7 +215,7 @@ __global__ void __launch_bounds__(256) k_mw_fit(const double *__restrict__ win, 
 	const unsigned jb = w == 0 ? j0_1 : w == 1 ? j0_2 : w == 2 ? j0_3 : j0_4;
 	const double nan = __longlong_as_double(0x7ff8000000000000ll), inf = __longlong_as_double(0x7ff0000000000000ll);
 	double *__restrict__ fo = fit + (row * W + w) * 6;
-	if (slot == MW_NOSLOT) { // the row does not take part
+	if (slot == NOSLOT) { // the row does not take part
 		if (d_win)
 			for (size_t i = (size_t)ja * 3 + lane; i < (size_t)jb * 3; i += 64) d_win[row * J * 3 + i] = nan;
 		if (d_spec)
@@ -287,10 +287,8 @@ extern "C" int tspws_hip_mwcs_rows(tspws_hip_plan *pl, const float *d_rows, size
 	// first what needs no plan
 	if (!d_rows || !d_ref || !par || !h_win || !d_fit) return fail(TSPWS_E_ARG, "mwcs_rows: NULL");
 	const MwPar P = *(const MwPar *)par;
-	if (const char *e = mw_par_error(P)) return fail(TSPWS_E_ARG, (std::string("mwcs_rows: ") + e).c_str());
-	if (!W || W > MW_WMAX) return fail(TSPWS_E_ARG, "mwcs_rows: 1 to 4 lag ranges");
-	for (unsigned w = 0; w < W; w++)
-		if (h_win[2 * w] >= h_win[2 * w + 1]) return fail(TSPWS_E_ARG, "mwcs_rows: an empty lag range (n0 >= n1)");
+	if (const char *e = mw_par_error(P)) return refuse("mwcs_rows", e);
+	if (const char *e = range_error(h_win, W, LAG_RANGES)) return refuse("mwcs_rows", e);
 	if (!std::isfinite(z)) return fail(TSPWS_E_ARG, "mwcs_rows: a NaN or infinite zero-lag position");
 	const unsigned long long Jn = mw_count_windows(h_win, W, P.L, P.hop);
 	if (!Jn) return fail(TSPWS_E_ARG, "mwcs_rows: no lag range holds a window");
@@ -299,8 +297,7 @@ extern "C" int tspws_hip_mwcs_rows(tspws_hip_plan *pl, const float *d_rows, size
 	const size_t N = pl->N;
 	if (ld < N) return fail(TSPWS_E_ARG, "mwcs_rows: row stride below the trace length");
 	if (ldr < N) return fail(TSPWS_E_ARG, "mwcs_rows: reference row stride below the trace length");
-	for (unsigned w = 0; w < W; w++)
-		if (h_win[2 * w + 1] > N) return fail(TSPWS_E_ARG, "mwcs_rows: a lag range past the trace length");
+	if (const char *e = range_past_error(h_win, W, N, LAG_RANGES)) return refuse("mwcs_rows", e);
 	if (!B || !M) return 0;
 	if ((unsigned long long)B * M > 0xfffffff0ull) return fail(TSPWS_E_ARG, "mwcs_rows: more than 2^32 - 16 rows");
 
@@ -309,16 +306,11 @@ extern "C" int tspws_hip_mwcs_rows(tspws_hip_plan *pl, const float *d_rows, size
 	const MwWins wl = mw_windows(h_win, W, P.L, P.hop);
 	std::vector<double> basis(mw_basis_layout(P).doubles);
 	mw_basis(P, basis.data());
-	std::vector<size_t> nrows0((size_t)B + 1, 0); // participating rows in front of ensemble b
-	for (unsigned b = 0; b < B; b++) {
-		size_t n = M;
-		if (h_mtr) { n = 0; for (unsigned m = 0; m < M; m++) n += h_mtr[(size_t)b * M + m] > 0; }
-		nrows0[b + 1] = nrows0[b] + n;
-	}
-	const std::vector<MwRound> rounds = mw_rounds(B, nrows0.data(), M, J, P, tspws_part_budget_bytes());
+	const std::vector<size_t> nrows0 = participating_rows0(h_mtr, B, M);
+	const std::vector<Round> rounds = mw_rounds(B, nrows0.data(), M, J, P, tspws_part_budget_bytes());
 	const unsigned ncg = (bins.Qp / MW_CT + MW_NT - 1) / MW_NT;
 	size_t max_tab = 0, max_spec = 0, max_win = 0;
-	for (const MwRound &r : rounds) {
+	for (const Round &r : rounds) {
 		const size_t nb = r.j1 - r.j0, nrows = nrows0[r.j1] - nrows0[r.j0];
 		// one workgroup per 4 waves: the grids of the three launches
 		const unsigned long long waves = std::max({((unsigned long long)(nrows + nb) * J + MW_ROWS - 1) / MW_ROWS * ncg, (unsigned long long)(nrows + nb) * J,
@@ -344,7 +336,7 @@ extern "C" int tspws_hip_mwcs_rows(tspws_hip_plan *pl, const float *d_rows, size
 	double *F = (double *)v;
 	if ((rc = scratch(pl, SCR_MWW, std::max<size_t>(max_win, 16), &v))) return rc;
 	double *win = (double *)v;
-	for (const MwRound &r : rounds) {
+	for (const Round &r : rounds) {
 		const size_t nb = r.j1 - r.j0, nrows = nrows0[r.j1] - nrows0[r.j0], row0 = r.j0 * (size_t)M;
 		stats.rounds++;
 		const MwTab o = mw_tab(P, J, nrows + nb, nb * M);

@@ -10,15 +10,14 @@
 // of 16.  What a round holds at a time: the partial sums of all its participating rows over the whole grid, the S^2 partial sums, its table
 // (together: the fixed part) and the stretched references of ONE chunk.  The first ensemble of a round is always taken with Ec >= 16 (one
 // ensemble x 16 stretches may exceed the budget on its own); the round extends while the fixed part and a chunk of 16 still fit; then Ec is
-// the largest multiple of 16 that fits.
+// the largest multiple of 16 that fits.  The round rule, participation and the slots are host_plan.h's.
 #pragma once
 
-#include "column_runs.h" // TableLayout
+#include "host_plan.h"
 
 #include <cstdint>
 
 enum { SR_SEG = 512, SR_ET = 16, SR_ROWS = 32, SR_WMAX = 4, SR_EMAX = 4096 }; // samples per segment, stretches per tile, rows per wave tile
-constexpr unsigned SR_NOSLOT = ~0u;
 
 struct SrSeg { unsigned long long n0, joff; unsigned len, plen, w, pad; };
 // up to SR_ROWS participating rows of ensemble b (bl: its index in the round): their partial-sum slots, and their row numbers in the list, start at slot0
@@ -49,7 +48,7 @@ inline SrCols sr_columns(const size_t *win, unsigned W)
 
 inline unsigned sr_epad(unsigned E) { return (E + SR_ET - 1) / SR_ET * SR_ET; }
 
-// the table block of a round: segments | the padded grid | tiles | participating rows (m) | slot of every (ensemble of the round, m) or SR_NOSLOT
+// the table block of a round: segments | the padded grid | tiles | participating rows (m) | slot of every (ensemble of the round, m) or NOSLOT
 struct SrTab { size_t segs, eps, tiles, list, slot_of, bytes; };
 inline SrTab sr_tab(size_t nseg, size_t epad, size_t ntiles, size_t nlist, size_t nall)
 {
@@ -71,9 +70,9 @@ inline SrPart sr_part(size_t nb, size_t nrows, size_t nseg, size_t epad)
 }
 inline size_t sr_s_bytes(size_t nb, size_t Ec, size_t J) { return nb * Ec * J * sizeof(double); }
 
-struct SrRound { size_t j0, j1; unsigned Ec, nchunks; };
+struct SrRound : Round { unsigned Ec, nchunks; };
 
-// nrows0[b] = participating rows in front of ensemble b (B + 1 entries); tiles of an ensemble: ceil(rows / SR_ROWS)
+// nrows0: participating_rows0; tiles of an ensemble: ceil(rows / SR_ROWS)
 inline size_t sr_tiles(const size_t *nrows0, size_t j0, size_t j1)
 {
 	size_t n = 0;
@@ -94,12 +93,10 @@ inline std::vector<SrRound> sr_rounds(size_t B, const size_t *nrows0, size_t M, 
 		const size_t f = sr_fixed_bytes(nrows0, j0, j1, M, E, c), s = sr_s_bytes(j1 - j0, Ec, c.J);
 		return f <= budget && s <= budget - f;
 	};
-	for (size_t j0 = 0, j1; j0 < B; j0 = j1) {
-		j1 = j0 + 1;
-		while (j1 < B && fits(j0, j1 + 1, SR_ET)) j1++;
+	for (const Round &r : whole_ensemble_rounds(B, [&](size_t j0, size_t j1) { return fits(j0, j1, SR_ET); })) {
 		unsigned Ec = SR_ET;
-		while (Ec < epad && fits(j0, j1, Ec + SR_ET)) Ec += SR_ET;
-		rounds.push_back({j0, j1, Ec, (epad + Ec - 1) / Ec});
+		while (Ec < epad && fits(r.j0, r.j1, Ec + SR_ET)) Ec += SR_ET;
+		rounds.push_back({r, Ec, (epad + Ec - 1) / Ec});
 	}
 	return rounds;
 }
@@ -114,19 +111,10 @@ inline size_t sr_fill_round(char *blob, const SrTab &t, const SrRound &r, size_t
 	for (size_t s = 0; s < c.segs.size(); s++) segs[s] = c.segs[s];
 	const unsigned epad = sr_epad(E);
 	for (unsigned e = 0; e < epad; e++) ep[e] = e < E ? eps[e] : 0.0; // (the pad stretches are never evaluated: their columns of S are zero)
-	size_t slot = 0, nt = 0;
-	for (size_t b = r.j0; b < r.j1; b++) {
-		const size_t first = slot;
-		for (size_t m = 0; m < M; m++) {
-			const bool in = !h_mtr || h_mtr[b * M + m] > 0;
-			slot_of[(b - r.j0) * M + m] = in ? (unsigned)slot : SR_NOSLOT;
-			if (in) list[slot++] = (unsigned)m;
-		}
-		for (size_t s0 = first; s0 < slot; s0 += SR_ROWS) {
-			SrTile d;
-			d.b = (unsigned)b; d.bl = (unsigned)(b - r.j0); d.count = (unsigned)std::min<size_t>(SR_ROWS, slot - s0); d.pad = 0; d.slot0 = s0;
-			tiles[nt++] = d;
-		}
-	}
-	return slot;
+	size_t nt = 0;
+	return fill_round_slots(slot_of, r, M, h_mtr, [&](size_t slot, size_t b, size_t m) {
+		list[slot] = (unsigned)m;
+		if (!nt || tiles[nt - 1].b != b || tiles[nt - 1].count == SR_ROWS) tiles[nt++] = {(unsigned)b, (unsigned)(b - r.j0), 0, 0, slot}; // the next tile of ensemble b
+		tiles[nt - 1].count++;
+	});
 }

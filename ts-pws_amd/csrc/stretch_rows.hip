@@ -209,7 +209,7 @@ __global__ void __launch_bounds__(256) k_sr_final(const double *__restrict__ dot
 	const unsigned slot = slot_of[rw];
 	const double nan = __longlong_as_double(0x7ff8000000000000ll);
 	double *__restrict__ fo = fit + o * 4;
-	if (slot == SR_NOSLOT) { // the row does not take part
+	if (slot == NOSLOT) { // the row does not take part
 		if (cc) for (unsigned e = lane; e < E; e += 64) cc[o * E + e] = nan;
 		if (lane == 0) { fo[0] = nan; fo[1] = nan; fo[2] = -1.0; fo[3] = 1.0; }
 		return;
@@ -264,31 +264,24 @@ extern "C" int tspws_hip_stretch_rows(tspws_hip_plan *pl, const float *d_rows, s
 	// first what needs no plan
 	if (!d_rows || !d_ref || !h_eps || !h_win || !d_fit) return fail(TSPWS_E_ARG, "stretch_rows: NULL");
 	if (!E || E > SR_EMAX) return fail(TSPWS_E_ARG, "stretch_rows: 1 to 4096 stretch factors");
-	if (!W || W > SR_WMAX) return fail(TSPWS_E_ARG, "stretch_rows: 1 to 4 windows");
+	if (const char *e = range_count_error(W, WINDOWS)) return refuse("stretch_rows", e);
 	for (unsigned e = 0; e < E; e++) {
 		if (!(fabs(h_eps[e]) <= 0.5)) return fail(TSPWS_E_ARG, "stretch_rows: a stretch factor that is NaN or outside [-0.5, 0.5]");
 		if (e && !(h_eps[e] > h_eps[e - 1])) return fail(TSPWS_E_ARG, "stretch_rows: the stretch factors must increase strictly");
 	}
 	if (!std::isfinite(z)) return fail(TSPWS_E_ARG, "stretch_rows: a NaN or infinite zero-lag position");
-	for (unsigned w = 0; w < W; w++)
-		if (h_win[2 * w] >= h_win[2 * w + 1]) return fail(TSPWS_E_ARG, "stretch_rows: an empty window (n0 >= n1)");
+	if (const char *e = range_empty_error(h_win, W, WINDOWS)) return refuse("stretch_rows", e);
 	if (!pl) return fail(TSPWS_E_ARG, "stretch_rows: NULL");
 	const size_t N = pl->N;
 	if (ld < N) return fail(TSPWS_E_ARG, "stretch_rows: row stride below the trace length");
 	if (ldr < N) return fail(TSPWS_E_ARG, "stretch_rows: reference row stride below the trace length");
-	for (unsigned w = 0; w < W; w++)
-		if (h_win[2 * w + 1] > N) return fail(TSPWS_E_ARG, "stretch_rows: a window past the trace length");
+	if (const char *e = range_past_error(h_win, W, N, WINDOWS)) return refuse("stretch_rows", e);
 	if (!B || !M) return 0;
 	if ((unsigned long long)B * M > 0xfffffff0ull) return fail(TSPWS_E_ARG, "stretch_rows: more than 2^32 rows");
 
 	const SrCols cols = sr_columns(h_win, W);
 	const unsigned nseg = (unsigned)cols.segs.size(), epad = sr_epad(E);
-	std::vector<size_t> nrows0((size_t)B + 1, 0); // participating rows in front of ensemble b
-	for (unsigned b = 0; b < B; b++) {
-		size_t n = M;
-		if (h_mtr) { n = 0; for (unsigned m = 0; m < M; m++) n += h_mtr[(size_t)b * M + m] > 0; }
-		nrows0[b + 1] = nrows0[b] + n;
-	}
+	const std::vector<size_t> nrows0 = participating_rows0(h_mtr, B, M);
 	const std::vector<SrRound> rounds = sr_rounds(B, nrows0.data(), M, E, cols, tspws_part_budget_bytes());
 	auto tab_of = [&](const SrRound &r) { return sr_tab(nseg, epad, sr_tiles(nrows0.data(), r.j0, r.j1), nrows0[r.j1] - nrows0[r.j0], (r.j1 - r.j0) * (size_t)M); };
 	size_t max_tab = 0, max_part = 0, max_s = 0;

@@ -30,8 +30,12 @@
 //                 dtw_plan.h, host only: parameters, lags per lane, samples and plane words per range, rounds, the table block)
 //   ftan_rows.hip      group arrivals per scale from those rows (its own slots: SCR_FTTAB the pass's table, SCR_FTY the round's coefficient
 //                 sets, SCR_FTP the partial results; ftan_plan.h, host only: classes of ensembles, items, tasks, rounds, the table block)
-//                 (batch_kernels.h: the kernels those units share; batch_host.h: their host scaffold -- upload lifetime, rounds)
-//   column_runs.h   host only: the group signature of the two-stage replicas' columns, runs, column bits, the layout of a table block
+//                 (batch_kernels.h: the kernels those units share; batch_host.h: their host scaffold -- upload lifetime, finish batches)
+//   host_plan.h     host only: what the host plans share, each rule stated once -- the layout of a table block, the rounds of whole ensembles,
+//                 which rows take part and their slots (NOSLOT), the largest count within a budget, task packing, the checks of a range list
+//   coef_rows.h     the chunk and round drivers of the units that work on coefficient sets (wxs_rows.hip, ftan_rows.hip): they own the ens
+//                 vector, the stats' counters, the sizes a pass reserves and the call's end; the pass itself stays in its unit
+//   column_runs.h   host only: the group signature of the two-stage replicas' columns, runs, column bits
 //   masked_tables.h host only: the run tables of the masked replicas of one ensemble (resample.hip), in steps
 //   comm.hip      trace shards on several devices of one process: RCCL all-reduce, sharded tspws_main driver
 //
@@ -56,7 +60,7 @@
 #include <vector>
 
 #include "tspws_hip.h"
-#include "column_runs.h" // Chunk, RunDesc, TableLayout: host-only definitions that the kernels' tables share with the CPU checks
+#include "column_runs.h" // Chunk, RunDesc, TableLayout (host_plan.h): host-only definitions that the kernels' tables share with the CPU checks
 
 #ifndef TSPWS_PI
 #define TSPWS_PI 3.14159265358979328

@@ -14,15 +14,14 @@
 // items share waves, and no item's sum depends on the run it is in.
 // ROUNDS.  tspws_hip_wxs_rows: whole ensembles whose coefficient sets ((M + 1) sets of ncoef complex doubles each), partial sums and table
 // stay inside the parts budget; the first ensemble of a round is always taken.  tspws_hip_wxs_coef (the sets are the caller's): chunks of
-// rows whose partial sums and table do.
+// rows whose partial sums and table do.  The round rule, the slots, the chunk search and the task packing are host_plan.h's.
 #pragma once
 
-#include "column_runs.h" // TableLayout
+#include "host_plan.h"
 
 #include <cstdint>
 
 enum { WX_SEG = 256, WX_TASK = 16, WX_WMAX = 4, WX_RMAX = 64, WX_NSUM = 9, WX_NFIT = 6 };
-constexpr unsigned WX_NOSLOT = ~0u;
 
 struct WxScale { unsigned L, D, Ns; int c; unsigned long long coef_off; double omega; }; // what the plan needs of a scale (omega = w0 / scale)
 struct WxBand { unsigned s_begin, s_end; };                                              // (tspws_band)
@@ -35,7 +34,7 @@ struct WxRow { unsigned row, ens; };  // a participating row: its coefficient se
 struct WxPlan {
 	unsigned W = 0;
 	std::vector<unsigned> used;  // scales in use, increasing
-	std::vector<unsigned> uidx;  // [S]: index into used, or WX_NOSLOT
+	std::vector<unsigned> uidx;  // [S]: index into used, or NOSLOT
 	std::vector<WxItem> items;
 	std::vector<WxTask> tasks;
 	std::vector<WxSpan> spans;   // [used][W]
@@ -60,7 +59,7 @@ inline WxPlan wx_plan(const WxScale *sc, unsigned S, size_t N, const WxBand *ban
 {
 	WxPlan p;
 	p.W = W;
-	p.uidx.assign(S, WX_NOSLOT);
+	p.uidx.assign(S, NOSLOT);
 	std::vector<char> in(S, 0);
 	for (unsigned r = 0; r < R; r++)
 		for (unsigned s = bands[r].s_begin; s < bands[r].s_end; s++) in[s] = 1;
@@ -79,18 +78,12 @@ inline WxPlan wx_plan(const WxScale *sc, unsigned S, size_t N, const WxBand *ban
 			}
 			p.spans.push_back(sp);
 		}
-	unsigned passes = 0;
-	for (unsigned i = 0; i < p.items.size(); i++) {
-		const unsigned c = (p.items[i].count + 63) / 64;
-		if (p.tasks.empty() || passes + c > WX_TASK) { p.tasks.push_back({i, 0}); passes = 0; }
-		p.tasks.back().n++;
-		passes += c;
-	}
+	pack_tasks(p.tasks, 0, (unsigned)p.items.size(), WX_TASK, [&](unsigned i) { return (p.items[i].count + 63) / 64; }, [](unsigned) { return false; });
 	return p;
 }
 
 // the table block of a pass over nrows rows of which nslots take part:
-// items | tasks | spans | index of every scale in `used` | bands | the participating rows | slot of every row or WX_NOSLOT
+// items | tasks | spans | index of every scale in `used` | bands | the participating rows | slot of every row or NOSLOT
 struct WxTab { size_t items, tasks, spans, uidx, bands, list, slot_of, bytes; };
 inline WxTab wx_tab(const WxPlan &p, unsigned R, size_t nslots, size_t nrows)
 {
@@ -109,37 +102,23 @@ inline size_t wx_pass_bytes(const WxPlan &p, unsigned R, size_t nrows) { return 
 // the coefficient sets of nb ensembles of M rows and one reference
 inline size_t wx_set_bytes(size_t nb, size_t M, size_t ncoef) { return nb * (M + 1) * ncoef * 2 * sizeof(double); }
 
-struct WxRound { size_t j0, j1; };
-
 // tspws_hip_wxs_rows: rounds of whole ensembles
-inline std::vector<WxRound> wx_rounds(size_t B, size_t M, size_t ncoef, const WxPlan &p, unsigned R, size_t budget)
+inline std::vector<Round> wx_rounds(size_t B, size_t M, size_t ncoef, const WxPlan &p, unsigned R, size_t budget)
 {
-	std::vector<WxRound> rounds;
-	auto fits = [&](size_t nb) {
-		const size_t a = wx_set_bytes(nb, M, ncoef), b = wx_pass_bytes(p, R, nb * M);
+	return whole_ensemble_rounds(B, [&](size_t j0, size_t j1) {
+		const size_t a = wx_set_bytes(j1 - j0, M, ncoef), b = wx_pass_bytes(p, R, (j1 - j0) * M);
 		return a <= budget && b <= budget - a;
-	};
-	for (size_t j0 = 0, j1; j0 < B; j0 = j1) {
-		j1 = j0 + 1;
-		while (j1 < B && fits(j1 + 1 - j0)) j1++;
-		rounds.push_back({j0, j1});
-	}
-	return rounds;
+	});
 }
 
-// tspws_hip_wxs_coef: the rows of a chunk (at least one)
+// tspws_hip_wxs_coef: the rows of a chunk (at least one; wx_pass_bytes is monotone in the rows)
 inline size_t wx_chunk_rows(size_t nrow, const WxPlan &p, unsigned R, size_t budget)
 {
-	size_t lo = 1, hi = nrow; // the largest n in [1, nrow] whose pass fits (wx_pass_bytes is monotone in n)
-	while (lo < hi) {
-		const size_t mid = lo + (hi - lo + 1) / 2;
-		if (wx_pass_bytes(p, R, mid) <= budget) lo = mid; else hi = mid - 1;
-	}
-	return lo;
+	return largest_fitting(nrow, [&](size_t n) { return wx_pass_bytes(p, R, n); }, budget);
 }
 
 // the table of a pass into blob (wx_tab's layout for the pass's own counts; zeroed by the caller); ens[nrows] = the reference set of every
-// row, or WX_NOSLOT for a row that does not take part.  Returns the participating rows.
+// row, or NOSLOT for a row that does not take part.  Returns the participating rows.
 inline size_t wx_fill(char *blob, const WxTab &t, const WxPlan &p, const WxBand *bands, unsigned R, const unsigned *ens, size_t nrows)
 {
 	std::copy(p.items.begin(), p.items.end(), (WxItem *)(blob + t.items));
@@ -148,18 +127,5 @@ inline size_t wx_fill(char *blob, const WxTab &t, const WxPlan &p, const WxBand 
 	std::copy(p.uidx.begin(), p.uidx.end(), (unsigned *)(blob + t.uidx));
 	std::copy(bands, bands + R, (WxBand *)(blob + t.bands));
 	WxRow *list = (WxRow *)(blob + t.list);
-	unsigned *slot_of = (unsigned *)(blob + t.slot_of);
-	size_t slot = 0;
-	for (size_t i = 0; i < nrows; i++) {
-		slot_of[i] = ens[i] == WX_NOSLOT ? WX_NOSLOT : (unsigned)slot;
-		if (ens[i] != WX_NOSLOT) list[slot++] = {(unsigned)i, ens[i]};
-	}
-	return slot;
-}
-
-inline size_t wx_count_slots(const unsigned *ens, size_t nrows)
-{
-	size_t n = 0;
-	for (size_t i = 0; i < nrows; i++) n += ens[i] != WX_NOSLOT;
-	return n;
+	return fill_row_slots((unsigned *)(blob + t.slot_of), ens, nrows, [&](size_t slot, unsigned e, size_t i) { list[slot] = {(unsigned)i, e}; });
 }

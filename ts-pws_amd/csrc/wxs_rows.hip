@@ -15,9 +15,8 @@
 // Nothing is atomic, every output has one writer, and the order of every sum depends on the scale, the window, the wrap rule and the band's
 // range alone: a repeated call is bit-identical, and nrow, B, M, the other bands and windows, the rounds and the padding change no bit.
 #include "tspws_internal.h"
-#include "batch_host.h"
+#include "coef_rows.h"
 #include "lane_reduce.h"
-#include "wxs_plan.h"
 
 static_assert(sizeof(WxBand) == sizeof(tspws_band) && sizeof(WxItem) == 32 && WX_SEG == 4 * 64, "the tables' layout");
 
@@ -106,7 +105,7 @@ __global__ void __launch_bounds__(256) k_wx_final(const double *__restrict__ par
 	const unsigned slot = slot_of[row];
 	const double nan = __longlong_as_double(0x7ff8000000000000ll);
 	double *__restrict__ fo = fit + out * WX_NFIT;
-	if (slot == WX_NOSLOT) { // the row does not take part
+	if (slot == NOSLOT) { // the row does not take part
 		if (sums)
 			for (int e = 0; e < WX_NSUM; e++) sums[out * WX_NSUM + e] = nan;
 		for (int e = 0; e < 5; e++) fo[e] = nan;
@@ -148,35 +147,31 @@ static int wx_check_tables(const tspws_hip_plan *pl, const char *who, double z, 
 	const std::string w(who);
 	if (!pl) {
 		if (!R || R > WX_RMAX) return fail(TSPWS_E_ARG, (w + ": 1 to 64 bands").c_str());
-		if (!W || W > WX_WMAX) return fail(TSPWS_E_ARG, (w + ": 1 to 4 windows").c_str());
+		if (const char *e = range_count_error(W, WINDOWS)) return refuse(who, e);
 		if (int rc = tspws_bands_check(nullptr, bands, R, who)) return rc;
-		for (unsigned i = 0; i < W; i++)
-			if (win[2 * i] >= win[2 * i + 1]) return fail(TSPWS_E_ARG, (w + ": an empty window (n0 >= n1)").c_str());
+		if (const char *e = range_empty_error(win, W, WINDOWS)) return refuse(who, e);
 		if (!std::isfinite(z)) return fail(TSPWS_E_ARG, (w + ": a NaN or infinite zero-lag position").c_str());
 		return 0;
 	}
 	if (int rc = tspws_bands_check(pl, bands, R, who)) return rc;
-	for (unsigned i = 0; i < W; i++)
-		if (win[2 * i + 1] > pl->N) return fail(TSPWS_E_ARG, (w + ": a window past the trace length").c_str());
+	if (const char *e = range_past_error(win, W, pl->N, WINDOWS)) return refuse(who, e);
 	return 0;
 }
 
 static WxPlan wx_plan_of(const tspws_hip_plan *pl, const tspws_band *bands, unsigned R, const size_t *win, unsigned W, int skip_wrapped)
 {
-	std::vector<WxScale> sc(pl->S);
-	for (unsigned s = 0; s < pl->S; s++) {
-		const ScaleDesc &d = pl->sc[s];
-		sc[s] = {d.L, d.D, d.Ns, d.c, d.coef_off, pl->w0 / d.scale}; // (rad per sample: tspws_bands_from_frequencies' centre frequency times 2 pi dt)
-	}
+	std::vector<WxScale> sc = wx_scales_of(pl);
+	for (unsigned s = 0; s < pl->S; s++) sc[s].omega = pl->w0 / pl->sc[s].scale; // (rad per sample: tspws_bands_from_frequencies' centre frequency times 2 pi dt)
 	return wx_plan(sc.data(), pl->S, pl->N, (const WxBand *)bands, R, win, W, skip_wrapped);
 }
 
-// one pass: the rows [0, nrows) of Yc against the sets ens[.] of Yr (WX_NOSLOT: the row does not take part); outputs from row `row0` on
+// one pass: the rows [0, nrows) of Yc against the sets ens[.] of Yr (NOSLOT: the row does not take part); outputs from row `row0` on; the
+// slots are reserved for a pass of max_rows rows
 static int wx_pass(tspws_hip_plan *pl, BatchCall &call, const char *who, const WxPlan &P, const tspws_band *bands, unsigned R, const double2 *Yc,
-                   const double2 *Yr, const unsigned *ens, size_t nrows, size_t row0, double z, size_t max_tab, size_t max_part, double *d_sums, double *d_fit)
+                   const double2 *Yr, const unsigned *ens, size_t nrows, size_t row0, double z, size_t max_rows, double *d_sums, double *d_fit)
 {
 	hipStream_t st = call.stream();
-	const size_t nslots = wx_count_slots(ens, nrows);
+	const size_t nslots = count_slots(ens, nrows), max_tab = wx_tab(P, R, max_rows, max_rows).bytes, max_part = wx_part_bytes(P, max_rows);
 	const WxTab o = wx_tab(P, R, nslots, nrows);
 	const unsigned nitems = (unsigned)P.items.size(), ntasks = (unsigned)P.tasks.size();
 	const unsigned long long nwork = (unsigned long long)nslots * ntasks, nout = (unsigned long long)nrows * P.W * R;
@@ -223,19 +218,10 @@ extern "C" int tspws_hip_wxs_coef(tspws_hip_plan *pl, const double *d_Yc, const 
 	HIP_TRY(hipSetDevice(pl->device));
 	BatchCall call(S_(s));
 	wx_stats_begin(pl, P);
-	pl->wxs_stats.rows = (unsigned)nrow;
-	std::vector<unsigned> ens(std::min(chunk, nrow));
-	for (size_t r0 = 0; r0 < nrow; r0 += chunk) {
-		const size_t n = std::min(chunk, nrow - r0);
-		for (size_t i = 0; i < n; i++) ens[i] = h_ens ? h_ens[r0 + i] : (unsigned)(r0 + i);
-		pl->wxs_stats.rounds++;
-		if (int rc = wx_pass(pl, call, who, P, h_bands, R, (const double2 *)d_Yc + r0 * pl->ncoef, (const double2 *)d_Yr, ens.data(), n, r0, z,
-		                     wx_tab(P, R, chunk, chunk).bytes, wx_part_bytes(P, std::min(chunk, nrow)), d_sums, d_fit))
-			return rc;
-	}
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(call.drain()); // outputs complete
-	return 0;
+	return coef_chunks(call, row_counters(pl->wxs_stats), (const double2 *)d_Yc, (const double2 *)d_Yr, pl->ncoef, h_ens, nrow, chunk,
+	                   [&](const double2 *Yc, const double2 *Yr, const unsigned *ens, size_t n, size_t row0, size_t max_rows) {
+		                   return wx_pass(pl, call, who, P, h_bands, R, Yc, Yr, ens, n, row0, z, max_rows, d_sums, d_fit);
+	                   });
 }
 
 extern "C" int tspws_hip_wxs_rows(tspws_hip_plan *pl, const float *d_rows, size_t ld, unsigned B, unsigned M, const unsigned *h_mtr, const float *d_ref,
@@ -253,40 +239,14 @@ extern "C" int tspws_hip_wxs_rows(tspws_hip_plan *pl, const float *d_rows, size_
 	if ((unsigned long long)B * M > 0xfffffff0ull) return fail(TSPWS_E_ARG, "wxs_rows: more than 2^32 - 16 rows");
 
 	const WxPlan P = wx_plan_of(pl, h_bands, R, h_win, W, skip_wrapped);
-	const size_t ncoef = pl->ncoef;
-	const std::vector<WxRound> rounds = wx_rounds(B, M, ncoef, P, R, tspws_part_budget_bytes());
-	size_t max_nb = 0;
-	for (const WxRound &r : rounds) max_nb = std::max(max_nb, r.j1 - r.j0);
+	const std::vector<Round> rounds = wx_rounds(B, M, pl->ncoef, P, R, tspws_part_budget_bytes());
 	HIP_TRY(hipSetDevice(pl->device));
-	hipStream_t st = S_(s);
-	BatchCall call(st);
+	BatchCall call(S_(s));
 	wx_stats_begin(pl, P);
-	int rc;
-	void *v;
-	if ((rc = scratch(pl, SCR_WXY, std::max<size_t>(wx_set_bytes(max_nb, M, ncoef), 16), &v))) return rc; // (the largest round's: the slot does not grow between rounds)
-	double2 *Y = (double2 *)v;
-	std::vector<unsigned> ens(max_nb * M);
-	for (const WxRound &r : rounds) {
-		const size_t nb = r.j1 - r.j0, nrows = nb * M;
-		double2 *Yc = Y, *Yr = Y + nrows * ncoef;
-		// the rows left out are transformed too: ONE forward call on the round's rows, one on its references
-		if ((rc = tspws_hip_forward_f32(pl, d_rows + r.j0 * M * ld, nrows, ld, (double *)Yc, st))) return rc;
-		if ((rc = tspws_hip_forward_f32(pl, d_ref + r.j0 * ldr, nb, ldr, (double *)Yr, st))) return rc;
-		for (size_t bl = 0; bl < nb; bl++)
-			for (size_t m = 0; m < M; m++) {
-				const bool in = !h_mtr || h_mtr[(r.j0 + bl) * M + m] > 0;
-				ens[bl * M + m] = in ? (unsigned)bl : WX_NOSLOT;
-				pl->wxs_stats.rows += in;
-				pl->wxs_stats.left_out += !in;
-			}
-		pl->wxs_stats.rounds++;
-		if ((rc = wx_pass(pl, call, who, P, h_bands, R, Yc, Yr, ens.data(), nrows, r.j0 * M, z, wx_tab(P, R, max_nb * M, max_nb * M).bytes,
-		                  wx_part_bytes(P, max_nb * M), d_sums, d_fit)))
-			return rc;
-	}
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(call.drain()); // outputs complete
-	return 0;
+	return coef_rounds(pl, call, row_counters(pl->wxs_stats), d_rows, ld, M, h_mtr, d_ref, ldr, 1, rounds, SCR_WXY,
+	                   [&](const double2 *Yc, const double2 *Yr, const unsigned *ens, size_t n, size_t row0, size_t max_rows) {
+		                   return wx_pass(pl, call, who, P, h_bands, R, Yc, Yr, ens, n, row0, z, max_rows, d_sums, d_fit);
+	                   });
 }
 
 extern "C" int tspws_hip_wxs_rows_stats(const tspws_hip_plan *pl, tspws_hip_wxs_stats *stats)
