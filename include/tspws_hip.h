@@ -947,6 +947,65 @@ int  tspws_ftan_windows(double dist, double vmin, double vmax, double dt, double
  * that order), written to T[S].  A NULL scale / T (with S > 0) and dt or w0 <= 0 (or not finite) return TSPWS_E_ARG. */
 int  tspws_ftan_periods(const double *scale, unsigned S, double w0, double dt, double *T);
 
+/* ---- the stack's coherence filter per trace ---- */
+/* The rows a dv/v time series is measured on -- one per day, or per short moving stack -- are the noisy ones.  The phase coherence of the
+ * whole ensemble is a time-scale filter for each of them (Baig et al. 2009, Hadziioannou et al. 2011, there with the S transform): with Y_i
+ * the frame coefficients of target i and W the weight that the stack applies to ST,
+ *   x~_i = (float) ICWT(Y_i W_b).
+ * Ensemble b is the traces [h_first[b], h_first[b+1]) of d_sigall, M_b of them; u_i is the unit phasor of trace i by the library's rule (a
+ * quotient that is no unit phasor adds nothing), PS_b = sum_i u_i.  Stage and counts follow tspws_hip_stack_batch: single-stage K = M_b and
+ * PS over the traces; two-stage (0 < Kmax <= M_b) PS over the Kmax partial stacks and K = Kmax.  W is the dimensionless weight per
+ * coefficient, the stack's without its ST and 1 / M factors, by the mode of (wu, unbiased, K) as in tspws_hip_weight; every FP64 operation
+ * below is rounded on its own (no contraction), in this order:
+ *   mode 0 (wu == 2)            g = 1 / (K K);  W = (PS.re PS.re + PS.im PS.im) g
+ *   mode 1 (wu == 1)            g = 1 / K;      W = hypot(PS.re, PS.im) g
+ *   mode 2 (any other wu)       W = pow(hypot(PS.re, PS.im) / K, wu)
+ *   mode 3 (wu == 2, unbiased, K != 1)   iK = 1 / K, iK1 = 1 / (K - 1);  px = PS.re iK, py = PS.im iK;  c = px px + py py;  W = (K c - 1) iK1
+ * (mode 3 can be negative, as in the reference) and the filtered coefficient is (Y.re W, Y.im W).  By linearity the mean of an ensemble's
+ * filtered traces is its tsPWS row, up to rounding.
+ * Leave-one-out (loo == 1, single-stage ensembles only): trace i is filtered with the W of PS_b - u_i (one subtraction per component) and
+ * K - 1, mode by K - 1 (K - 1 == 1 falls back to mode 0 by the reference's rule), so that its own phase does not vouch for itself; u_i is
+ * what the accumulation added for it -- nothing when the rule skipped it.  An ensemble with M_b < 2 gives NaN rows and counts as left out.
+ *
+ * tspws_hip_filter_coef: the weight applied to coefficient sets of the caller's.  d_Y is [nrow][ncoef] complex (tspws_hip_forward_f32's
+ * layout), h_ens[nrow] names the ensemble of every row (NULL: nrow == B, row i of ensemble i), d_PS is [B][ncoef] complex, h_K[B] the
+ * counts; d_out [nrow][ncoef] receives Y W (NULL: in place).  The bits of a row depend on its own set, its ensemble's PS and K and the mode
+ * alone, not on nrow, the other rows or how a caller cuts the rows into calls.  NULL d_Y / d_PS / h_K / plan, loo outside {0, 1}, a NaN or
+ * infinite wu, a count of 0 (loo: below 2), an h_ens entry >= B (or no h_ens with nrow != B), more than 65535 ensembles and more than
+ * 2^32 - 16 rows return TSPWS_E_ARG ("filter_coef: ..."); nrow == 0 or B == 0 returns 0 and does nothing.
+ * tspws_hip_filter_traces: the whole call.  `p` must be resolved; wu, unbiased and Kmax are taken from it.  Targets: with d_rows == NULL the
+ * ensembles' own traces, and d_out is [h_first[B] - h_first[0]][ldo] floats, row i - h_first[0] being trace i (an empty ensemble writes
+ * nothing); else M rows per ensemble, d_rows [B][M][ldr] floats with h_mtr [B][M] host counts as for tspws_hip_stretch_rows (NULL: every
+ * row; a count of 0: the row is left out), filtered with the W of the ensemble's traces, and d_out is [B][M][ldo] (rows left out and the
+ * rows of an empty ensemble: NaN).  Without d_rows, M must be 0 and h_mtr NULL.  Columns max .. ld-1 are never read, columns max .. ldo-1
+ * never written.
+ * In rounds of whole ensembles whose blocks stay within TSPWS_PART_MB: the targets' coefficient sets (16 ncoef B a row), the FP64 rows of
+ * the inverse, a PS and a W plane per ensemble and one ST plane.  A round is ONE tspws_hip_forward_f32 on its targets, PS per ensemble from
+ * tspws_hip_accumulate on the sets just made (trace targets, single-stage), tspws_hip_stacks_float on the ensemble's traces (row targets)
+ * or tspws_hip_partial_stacks + tspws_hip_stacks_double (two-stage), the weights, tspws_hip_inverse (ONE call, unless its octave buffer
+ * for all the round's rows would exceed the budget: then on as many rows at a time as fit) and the cast.  An ensemble whose
+ * blocks alone exceed the budget gets its PS first, chunk by chunk, and its targets are then transformed a second time in chunks.
+ * Refusals, TSPWS_E_ARG ("filter_traces: ...") before any device work, outputs untouched, the checks that need no plan first: NULL p /
+ * h_first / d_out (d_sigall when there are traces), decreasing offsets, loo outside {0, 1}, d_rows without M, M or h_mtr without d_rows, loo
+ * with d_rows, loo with a two-stage ensemble, more than 2^32 - 16 target rows; then a NULL plan and ld, ldr or ldo < max.  B == 0 returns 0
+ * and does nothing.  Nothing is atomic, every output has one writer, a repeated call is bit-identical.  The call waits for `stream`: on
+ * return the outputs are complete. */
+int  tspws_hip_filter_coef(tspws_hip_plan *plan, const double *d_Y, const unsigned *h_ens, size_t nrow, const double *d_PS, const unsigned *h_K,
+                           unsigned B, double wu, int unbiased, int loo, double *d_out, void *stream);
+int  tspws_hip_filter_traces(tspws_hip_plan *plan, const t_tsPWS *p, const float *d_sigall, size_t ld, const size_t *h_first, unsigned B,
+                             const float *d_rows, size_t ldr, unsigned M, const unsigned *h_mtr, int loo, float *d_out, size_t ldo, void *stream);
+/* How the plan's last tspws_hip_filter_traces / tspws_hip_filter_coef call that did work went (all zero before the first one). */
+typedef struct {
+	unsigned rounds;       /* rounds of whole ensembles (filter_coef: chunks of rows)                                  */
+	unsigned rows;         /* target rows that were filtered                                                           */
+	unsigned left_out;     /* rows left out: by h_mtr, of an empty ensemble, or under loo of an ensemble with M_b < 2  */
+	unsigned single_stage; /* ensembles with traces, by stage rule ...                                                 */
+	unsigned two_stage;
+	unsigned empty;        /* ... and those without                                                                    */
+	unsigned twice;        /* ensembles whose traces were transformed twice (their blocks alone exceed the budget)     */
+} tspws_hip_filter_stats;
+int  tspws_hip_filter_traces_stats(const tspws_hip_plan *plan, tspws_hip_filter_stats *stats);
+
 /* ---- convergence curves ------------------------------------------------------------------------ */
 /* Similarity / misfit of the stack of the first i+1 traces against a reference, for i = 0..mtr-1
  * (ts_pws1f_lib.c:247-314, similarity :433-449, misfit :452-462).  d_ref_ts / d_ref_ls are [max] floats on the

@@ -191,6 +191,9 @@ SYMBOLS = {
     "tspws_hip_ftan_rows_stats": (_i, [_vp, _vp]),
     "tspws_ftan_windows": (_i, [_d, _d, _d, _d, _d, _sz, _i, _vp]),
     "tspws_ftan_periods": (_i, [_vp, _u, _d, _d, _vp]),
+    "tspws_hip_filter_coef": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _u, _d, _i, _i, _vp, _vp]),
+    "tspws_hip_filter_traces": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _vp, _sz, _u, _vp, _i, _vp, _sz, _vp]),
+    "tspws_hip_filter_traces_stats": (_i, [_vp, _vp]),
     "tspws_mwcs_basis_size": (_sz, [_vp]),
     "tspws_mwcs_basis": (_i, [_vp, _vp]),
     "tspws_hip_selective_stack_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _u, _i, _i, _d, _u, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1183,6 +1186,67 @@ class Plan:
     def ftan_rows_stats(self):
         """How the last ftan_rows / ftan_coef call that did work went (tspws_hip_ftan_rows_stats): dict(rounds, rows, left_out, items, classes)."""
         return self._stats("ftan_rows_stats", ("rounds", "rows", "left_out", "items", "classes"))
+
+    def filter_coef(self, Y, PS, K, ens=None, loo=False, out=None):
+        """The stack's coherence weight applied to coefficient sets (tspws_hip_filter_coef): `Y` [nrow][ncoef] and `PS` [B][ncoef]
+        (complex128, as for inverse), `K` = the uint32 [B] counts, `ens` = None (nrow == B, row i of ensemble i) or the uint32 [nrow] ensemble
+        of every row; wu and unbiased are the plan's parameters.  loo=True filters row i with the weight of PS - u_i and K - 1.  Returns
+        Y W as a complex128 cuda tensor [nrow][ncoef]: new (NaN before the call) or `out` as given; out=Y (the same device tensor) works in
+        place.  Synchronises."""
+        import numpy as np
+        import torch
+        Yd, _ = self._coef_sets(Y, "nrow")
+        PSd, _ = self._coef_sets(PS, "B")
+        nrow, B = Yd.shape[0], PSd.shape[0]
+        K = _host_array(K, "K", np.uint32, (B,))
+        ens = _host_array(ens, "ens", np.uint32, (nrow,), optional=True)
+        if ens is None and nrow != B:
+            raise TspwsError(f"without ens, Y and PS must hold as many sets ({nrow} and {B})")
+        if out is not None and out is Y:  # in place: d_out == NULL
+            o = None
+        else:
+            o = torch.full((nrow, self.ncoef), complex(float("nan"), float("nan")), dtype=torch.complex128, device=Yd.device) if out is None else out
+            self._need(o, "out", "complex128", (nrow, self.ncoef))
+        p = self.params
+        check(self.lib.tspws_hip_filter_coef(self.h, Yd.data_ptr(), ens.ctypes.data if ens is not None else None, nrow, PSd.data_ptr(), K.ctypes.data, B,
+                                             float(p.wu), int(p.unbiased), int(bool(loo)), o.data_ptr() if o is not None else None, self._stream()),
+              "filter_coef")
+        return Yd if o is None else o
+
+    def filter_traces(self, traces, first, rows=None, mtr=None, loo=False, out=None):
+        """The stack's coherence filter per trace (tspws_hip_filter_traces): x~_i = ICWT(Y_i W_b), W_b the weight that the stack of ensemble b
+        = rows [first[b], first[b+1]) of the float32 [mtr][N] device tensor `traces` applies to its linear stack.  Targets: the ensembles' own
+        traces -- returns float32 cuda [T][N], T = first[B] - first[0], row i - first[0] = trace i filtered --, or `rows` (float32 cuda
+        [B][M][N] as for stretch_rows, with `mtr` = None or their uint32 [B][M] counts: a count of 0 leaves the row out) -- returns [B][M][N].
+        loo=True (trace targets, single-stage ensembles): trace i is filtered without its own phasor.  Rows left out hold NaN.  `out` = None or
+        the contiguous float32 cuda tensor of that shape to write; a new output holds NaN before the call.  The mean of an ensemble's filtered
+        traces is its ts row of stack_batch.  Synchronises."""
+        import numpy as np
+        import torch
+        ntr, ld = self._traces(traces)
+        f, B, T = _offsets(first, ntr)
+        if rows is None:
+            if mtr is not None:
+                raise TspwsError("mtr needs rows")
+            shape, ldr, Mn = (T, self.N), 0, 0
+        else:
+            Br, Mn, ldr = self._strided_rows(rows)
+            if Br != B:
+                raise TspwsError(f"rows must hold the B = {B} ensembles of first, got {Br}")
+            mtr = _host_array(mtr, "mtr", np.uint32, (B, Mn), optional=True)
+            shape = (B, Mn, self.N)
+        o = torch.full(shape, float("nan"), dtype=torch.float32, device=traces.device) if out is None else out
+        self._need(o, "out", "float32", shape)
+        if B and o.numel():  # (an empty tensor has no address)
+            check(self.lib.tspws_hip_filter_traces(self.h, C.byref(self.params), traces.data_ptr() if ntr else None, ld, f.ctypes.data, B,
+                                                   rows.data_ptr() if rows is not None else None, ldr, Mn, mtr.ctypes.data if mtr is not None else None,
+                                                   int(bool(loo)), o.data_ptr(), self.N, self._stream()), "filter_traces")
+        return o
+
+    def filter_traces_stats(self):
+        """How the last filter_traces / filter_coef call that did work went (tspws_hip_filter_traces_stats): dict(rounds, rows, left_out,
+        single_stage, two_stage, empty, twice)."""
+        return self._stats("filter_traces_stats", ("rounds", "rows", "left_out", "single_stage", "two_stage", "empty", "twice"))
 
     def convergence(self, traces, ref_ts, ref_ls, steps=False):
         """Convergence curves of ONE ensemble (tspws_hip_convergence) on device tensors: `traces` float32 [mtr][N], `ref_ts` / `ref_ls`

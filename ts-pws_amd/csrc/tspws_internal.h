@@ -30,6 +30,9 @@
 //                 dtw_plan.h, host only: parameters, lags per lane, samples and plane words per range, rounds, the table block)
 //   ftan_rows.hip      group arrivals per scale from those rows (its own slots: SCR_FTTAB the pass's table, SCR_FTY the round's coefficient
 //                 sets, SCR_FTP the partial results; ftan_plan.h, host only: classes of ensembles, items, tasks, rounds, the table block)
+//   filter_traces.hip  the stack's coherence filter per trace or per row (its own slots: SCR_CFTAB the pass's table, SCR_CFY the pass's
+//                 coefficient sets, SCR_CFX the inverse's rows, SCR_CFP the ST / PS / W planes, SCR_CFR a two-stage ensemble's partial stacks;
+//                 filter_plan.h, host only: costs, rounds, chunks, slabs, the table block)
 //                 (batch_kernels.h: the kernels those units share; batch_host.h: their host scaffold -- upload lifetime, finish batches)
 //   host_plan.h     host only: what the host plans share, each rule stated once -- the layout of a table block, the rounds of whole ensembles,
 //                 which rows take part and their slots (NOSLOT), the largest count within a budget, task packing, the checks of a range list
@@ -189,7 +192,7 @@ struct AccExtra {
 
 // (SCR_BTAB, SCR_ROWY, SCR_ROWX: the round's tables, the weighted sets of a finish batch and their reconstructions of whichever batched unit is
 // running: they never run side by side on one plan, and none keeps a pointer into these slots across a call into another unit)
-enum { SCR_Y = 0, SCR_PART, SCR_XT, SCR_OBUF, SCR_SEL, SCR_SUBST, SCR_CONV, SCR_CHUNK, SCR_P, SCR_STPS, SCR_OUT, SCR_X2, SCR_CLS, SCR_JKP, SCR_JKOUT, SCR_TAB, SCR_FZ, SCR_JKTAB, SCR_SPA, SCR_SPB, SCR_SPG, SCR_SPH, SCR_SPM, SCR_SPK, SCR_GEMM, SCR_J1TAB, SCR_J1PL, SCR_J1T, SCR_BTAB, SCR_BXG, SCR_BY, SCR_BX, SCR_BP, SCR_ROWY, SCR_ROWX, SCR_JBPL, SCR_JBT, SCR_J2P, SCR_J2ST, SCR_CBX, SCR_CBST, SCR_CBP, SCR_CBM, SCR_SBPL, SCR_RBTAB, SCR_TSTAB, SCR_TSP, SCR_TSOUT, SCR_SRTAB, SCR_SRS, SCR_SRP, SCR_WXTAB, SCR_WXY, SCR_WXP, SCR_MWTAB, SCR_MWF, SCR_MWW, SCR_DTTAB, SCR_DTP, SCR_FTTAB, SCR_FTY, SCR_FTP, SCR_N };
+enum { SCR_Y = 0, SCR_PART, SCR_XT, SCR_OBUF, SCR_SEL, SCR_SUBST, SCR_CONV, SCR_CHUNK, SCR_P, SCR_STPS, SCR_OUT, SCR_X2, SCR_CLS, SCR_JKP, SCR_JKOUT, SCR_TAB, SCR_FZ, SCR_JKTAB, SCR_SPA, SCR_SPB, SCR_SPG, SCR_SPH, SCR_SPM, SCR_SPK, SCR_GEMM, SCR_J1TAB, SCR_J1PL, SCR_J1T, SCR_BTAB, SCR_BXG, SCR_BY, SCR_BX, SCR_BP, SCR_ROWY, SCR_ROWX, SCR_JBPL, SCR_JBT, SCR_J2P, SCR_J2ST, SCR_CBX, SCR_CBST, SCR_CBP, SCR_CBM, SCR_SBPL, SCR_RBTAB, SCR_TSTAB, SCR_TSP, SCR_TSOUT, SCR_SRTAB, SCR_SRS, SCR_SRP, SCR_WXTAB, SCR_WXY, SCR_WXP, SCR_MWTAB, SCR_MWF, SCR_MWW, SCR_DTTAB, SCR_DTP, SCR_FTTAB, SCR_FTY, SCR_FTP, SCR_CFTAB, SCR_CFY, SCR_CFX, SCR_CFP, SCR_CFR, SCR_N };
 
 struct OctDesc; // inverse work items (inv_poly.h)
 struct TLItem;  // many-trace forward work items (fwd_tl.h)
@@ -303,6 +306,7 @@ struct tspws_hip_plan {
 	tspws_hip_mwcs_stats mwcs_stats{}; // ... and the last moving-window cross-spectrum call (mwcs_rows.hip)
 	tspws_hip_dtw_stats dtw_stats{}; // ... and the last dynamic time warping call (dtw_rows.hip)
 	tspws_hip_ftan_stats ftan_stats{}; // ... and the last group-arrival call (ftan_rows.hip)
+	tspws_hip_filter_stats filter_stats{}; // ... and the last coherence-filter call (filter_traces.hip)
 };
 
 int tspws_scratch(tspws_hip_plan *p, int slot, size_t bytes, void **out);
